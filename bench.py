@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: training rays/s of EndoSurf's renderer hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5]
+    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--dump-outputs DIR]
 
 N > 1: one rank per GPU over RCCL.  Either launched by ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N``
 (RANK / LOCAL_RANK / WORLD_SIZE in the environment) or directly as ``python bench.py --gpus N``, which re-executes itself under
@@ -15,6 +15,12 @@ Workloads (BASELINE.json ``configs``; all synthetic rays / targets resident in H
   --config 4  base_d1k1.yml networks (use_deform False), 1024 rays per GPU (4096-ray batch over 4 GPUs), full training step.
   --config 5  one 640x512 frame per step, forward only, hipGraph-captured 2048-ray chunks, frame rows split over the ranks.
 ``--mode forward`` times the renderer forward of the chosen training configuration instead.
+``--dump-outputs DIR`` writes what the last timed step of the headline workload returned to its caller as ``DIR/<name>.npy`` (float32, at
+most 64 MB in all; ``Workload.dump_outputs``).  Weights, batches and random draws are seeded, so two builds run with the same arguments see the
+same inputs and their dumps compare array for array.  With ``ES_DETERMINISTIC=1`` two runs of one build agree bit for bit
+(tests/test_gpu_bench_dp.py).  In the default mode the backward's fp32 atomics sum in another order every run and training amplifies it: three
+runs of ONE build (``--steps 50 --warmup 5``) differed by 6e-7 in the loss, 8e-6 of the largest element in ``params``, 1e-4 in the colour / depth
+maps and up to 1e-2 of the largest element in the per-sample arrays (``weights``, ``gradients_o``: single samples of the hierarchical sampling move).
 
 The DEFAULT invocation (config 2, training) appends, after the headline and outside its timed region, ``cpu_baseline`` and ``extras``:
 cfg2 forward-only, cfg2 in the opt-in split-precision mode, cfg3, cfg4 and one cfg5 frame -- each ``{ms_per_step, value,
@@ -58,6 +64,7 @@ CONFIGS = {
 MAC_D, MAC_S, MAC_C = 459520, 544512, 638208
 PEAK_F32_MFMA = 157.3      # TFLOP/s, dense v_mfma_f32_32x32x2_f32 (MI355X_MICROARCH.md)
 PEAK_BF16_MFMA = 2500.0    # TFLOP/s, dense v_mfma_f32_32x32x16_bf16 (same table); used for the opt-in split-precision kernels only
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs writes at most this much in all (file headers included)
 
 
 def render_cfg(c):
@@ -400,6 +407,7 @@ class Workload:
         self.ctx, self.cfg, self.mode, self.config_id, self.split, self.chunk, self.rays_override = ctx, cfg, mode, config_id, bool(split), chunk, rays
         self.graph, self.frame_graph = bool(graph) and mode == "train", frame_graph
         self.graph_probe = False          # set by main() for the headline workload of an N > 1 run (or --graph-probe)
+        self.dump_dir = None              # set by main() for the headline workload (--dump-outputs)
         torch.manual_seed(0)
         self.renderer = EndoSurfRenderer(render_cfg(cfg), dict(NET_CFG, use_deform=cfg["use_deform"]), device=ctx.dev)
         if split:
@@ -436,23 +444,53 @@ class Workload:
         b = self.batches[i % len(self.batches)]
         if self.mode == "train":
             if self.use_graph:
-                self.trainer.train_step_graph(b, i + 1)
-            else:
-                self.trainer.update_learning_rate(i + 1)
-                self.trainer.train_step(b, i + 1)
-        else:
-            with torch.no_grad():
-                self.renderer(b["rays"], iter_step=i + 1)
+                return self.trainer.train_step_graph(b, i + 1)
+            self.trainer.update_learning_rate(i + 1)
+            return self.trainer.train_step(b, i + 1)
+        with torch.no_grad():
+            return self.renderer(b["rays"], iter_step=i + 1)
 
-    def timed(self, first, n):
-        """EXACTLY n steps bracketed by barrier + synchronize on both sides; -> (max over ranks, this rank's) seconds."""
+    def timed(self, first, n, dump_dir=None):
+        """EXACTLY n steps bracketed by barrier + synchronize on both sides; -> (max over ranks, this rank's) seconds.
+        ``dump_dir``: once the clock has stopped, rank 0 writes what the LAST of the n steps returned (dump_outputs)."""
         self.ctx.barrier()
         t0 = time.perf_counter()
-        for i in range(n):
+        for i in range(n - 1):
             self.step(first + i)
+        out = self.step(first + n - 1)
         self.ctx.barrier()
         dt = time.perf_counter() - t0
+        if dump_dir and self.ctx.rank == 0:      # (before any later step: a step's results may live in workspace the next one reuses)
+            self.dump_outputs(out, dump_dir)
         return self.ctx.max_over_ranks(dt), dt
+
+    def dump_outputs(self, out, dump_dir):
+        """``--dump-outputs``: the arrays a caller of ``step`` receives, one ``<name>.npy`` (float32) each.  Training: the loss, its six
+        terms (``loss_<term>``), the render's dictionary and ``params``, the flat parameter buffer the step has just updated (the one
+        result that carries the backward and Adam); forward: the render's dictionary; frame: colour / depth / normal.  (N > 1: taken
+        from the eager timed window, also when the graph-probe rule makes the replayed step the headline.)"""
+        import numpy as np
+        import torch
+        if self.mode != "train":
+            named = dict(out)
+        else:
+            if torch.is_tensor(out):      # the whole-step hipGraph returns the loss only
+                named = dict(loss=out)
+            else:
+                loss, terms, ret = out
+                named = dict(ret, loss=loss, **{"loss_" + k: v for k, v in terms.items()})
+            named["params"] = self.renderer.model._flat
+        arrays = {k: v.detach().to("cpu", torch.float32).contiguous().numpy() for k, v in named.items() if torch.is_tensor(v)}
+        os.makedirs(dump_dir, exist_ok=True)
+        # DUMP_BYTES in all (128: a .npy header), smallest array first, so that what a small array leaves of its share goes to the larger
+        # ones; an array over its share is written as a fixed (seed 0) sample of its elements, in their order
+        left, n = (DUMP_BYTES - 128 * len(arrays)) // 4, len(arrays)
+        for k in sorted(arrays, key=lambda k: arrays[k].size):
+            a, share = arrays[k], left // n
+            if a.size > share:
+                a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+            left, n = left - a.size, n - 1
+            np.save(os.path.join(dump_dir, k + ".npy"), a)
 
     def host_issue_ms(self, first, n=5):
         """CPU time to ENQUEUE one step (no synchronisation inside; the queue is drained before each sample so that no launch call blocks
@@ -497,7 +535,7 @@ class Workload:
             eng.march_block = 0          # headline: the data-independent step (every ray's 128 marching proposals, like the reference)
         for i in range(warmup):
             self.step(i)
-        dt, dt_local = self.timed(warmup, steps)
+        dt, dt_local = self.timed(warmup, steps, dump_dir=self.dump_dir)
         nxt = warmup + steps
         # the same step with ray marching's early exit (blocks of 32 proposals; tiles whose rays have all passed their first sign change
         # return at once; results bit-identical): data-dependent, reported as an extra
@@ -950,7 +988,15 @@ def main():
                     help="data-parallel training: the gradient all-reduce as a pipeline of three buckets, two of them on a side stream under "
                          "the remaining weight-gradient launches (Trainer(overlap_allreduce=True); opt-in until a multi-GPU run has measured it)")
     ap.add_argument("--chunk", type=int, default=2048, help="frame mode: rays per chunk (the reference's demo.ray_batch is 2048)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned to its caller as DIR/<name>.npy (float32, at most 64 MB in "
+                         "all; rank 0's at N > 1): weights, batches and random draws are seeded, so two builds run with the same arguments can "
+                         "be compared array for array")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.refseq_only:
+        ap.error("--dump-outputs writes the headline workload's results: not available with --refseq-only")
 
     backend = os.environ.get("ES_DIST_BACKEND", "nccl")
     if args.gpus > 1 and backend == "nccl":
@@ -996,6 +1042,7 @@ def main():
     # ---- headline ---------------------------------------------------------------------------------------------------------------
     wl = Workload(ctx, args.config, mode=args.mode, split=args.split_precision, rays=args.rays, chunk=args.chunk, graph=args.graph,
                   frame_graph=not args.no_graph)
+    wl.dump_dir = args.dump_outputs
     wl.graph_probe = (world > 1 or args.graph_probe) and wl.mode == "train" and not args.graph and not args.split_precision
     m = wl.measure(args.warmup, args.steps, early_exit_extra=not args.headline_only)
     proof = collective_proof(ctx, wl, m["dt_local"]) if dist_on else None

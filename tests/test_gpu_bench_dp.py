@@ -47,32 +47,38 @@ def test_bench_two_ranks_one_gpu(mode):
         assert d["extras"] is None and d["config"]["frame_rows_per_rank"] == [256, 256] and d["config"]["rays_per_step_whole_job"] == 512 * 640
 
 
-def test_bench_eight_ranks_one_gpu_cold_run_kit():
-    """The line of an 8-rank run must be diagnosable: eight ranks (gloo, one GPU, a 64-ray batch each) -- the
-    collective saw all eight, every rank reports its host issue time per step, its GPU-idle estimate (eager step - the same step replayed
-    from the whole-step hipGraph) and the host cores it was pinned to, the fallback rule was evaluated, and after all steps the eight
+# every rank opens the one GPU, beside the launcher (torch.distributed.run asks for the device count) and the pytest process that starts
+# them: five processes on a device that other jobs may share.  More than two ranks is what the per-rank diagnostics need.
+MANY_RANKS = 3
+
+
+def test_bench_many_ranks_one_gpu_cold_run_kit():
+    """The line of a many-rank run must be diagnosable: MANY_RANKS ranks (gloo, one GPU, a 64-ray batch each) -- the
+    collective saw all of them, every rank reports its host issue time per step, its GPU-idle estimate (eager step - the same step replayed
+    from the whole-step hipGraph) and the host cores it was pinned to, the fallback rule was evaluated, and after all steps the
     replicas hold bit-identical parameters."""
+    n = MANY_RANKS
     env = dict(os.environ, ES_DIST_BACKEND="gloo", OMP_NUM_THREADS="2")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
+           "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1",
            "--no-cpu-baseline", "--rays", "64", "--headline-only"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500, cwd=REPO)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
     d = json.loads(lines[0])
-    assert d["n_gpus"] == 8 and d["config"]["parallelism"] == "dp8" and d["config"]["rays_per_step_whole_job"] == 8 * 64 and d["value"] > 0
-    assert d["ranks_seen_by_collective"] == 8
+    assert d["n_gpus"] == n and d["config"]["parallelism"] == "dp%d" % n and d["config"]["rays_per_step_whole_job"] == n * 64 and d["value"] > 0
+    assert d["ranks_seen_by_collective"] == n
     assert d["collective_proof"]["replicas_bit_identical"] is True, d["collective_proof"]
     pr = d["per_rank"]
-    assert sorted(r["rank"] for r in pr) == list(range(8))
+    assert sorted(r["rank"] for r in pr) == list(range(n))
     for r in pr:
         assert r["host_issue_ms"] > 0 and r["gpu_idle_ms"] >= 0 and r["ms_per_step"] > 0 and "pinned" in r["affinity"], r
     pinned = [r["affinity"] for r in pr if r["affinity"]["pinned"]]
-    if pinned:          # (fewer than 8 usable host cores: nothing is pinned, and the line says why)
-        assert len(pinned) == 8
+    if pinned:          # (fewer usable host cores than ranks: nothing is pinned, and the line says why)
+        assert len(pinned) == n
         spans = sorted((a["first"], a["last"]) for a in pinned)
-        assert all(spans[i][1] < spans[i + 1][0] for i in range(7)), spans          # disjoint core sets
+        assert all(spans[i][1] < spans[i + 1][0] for i in range(n - 1)), spans          # disjoint core sets
     else:
         assert all("reason" in r["affinity"] for r in pr)
     assert 0 < d["host_issue_ms_min"] <= d["host_issue_ms_max"] and 0 <= d["gpu_idle_ms_min"] <= d["gpu_idle_ms_max"]
@@ -131,6 +137,30 @@ def test_bench_default_line_carries_extras():
     assert "_x3" in sp["kernel"] and sp["peak"] == 2500.0            # the mode's roofline is taken on a bf16-pipe kernel
     assert sp["pipes"]["bf16"]["ms"] > 0 and sp["pipes"]["fp32"]["ms"] > 0 and 0 < sp["pipes"]["bf16"]["frac_of_2500"] < 1
     assert "1 x 2500" not in json.dumps(sp)
+
+
+def test_bench_dump_outputs_same_inputs_every_run(tmp_path):
+    """``--dump-outputs DIR``: the last timed step's results as DIR/<name>.npy.  Weights, batches and random draws are seeded, so two runs
+    of the same command see the same inputs: with the fixed-order reductions (ES_DETERMINISTIC=1) their dumps agree bit for bit, the
+    parameters after the step's update included -- and the dump is of the step ``--steps`` ends on (another step count: other results)."""
+    import numpy as np
+
+    def run(name, steps):
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline", "--headline-only",
+               "--dump-outputs", str(tmp_path / name)]
+        out = subprocess.run(cmd, env=dict(os.environ, ES_DETERMINISTIC="1"), capture_output=True, text=True, timeout=600, cwd=REPO)
+        assert out.returncode == 0, out.stderr[-3000:]
+        d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == steps and d["value"] > 0
+        return {f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))}
+    a, b, c = run("a", 2), run("b", 2), run("c", 3)
+    assert set(a) >= {"loss", "loss_color", "loss_surf_neig", "color_map", "depth_map", "weights", "gradients_o", "params"} and set(a) == set(b) == set(c)
+    assert a["color_map"].shape == (1024, 3) and a["weights"].shape == (1024, 64) and a["params"].shape == (1654951,) and a["loss"].shape == ()
+    assert sum(v.nbytes for v in a.values()) < 64e6
+    for k, v in a.items():
+        assert v.dtype == np.float32 and np.isfinite(v).all(), k
+        assert np.array_equal(v, b[k]), (k, float(np.abs(v - b[k]).max()))
+    assert not np.array_equal(a["color_map"], c["color_map"]) and not np.array_equal(a["params"], c["params"])
 
 
 @pytest.mark.parametrize("config", [3, 4])

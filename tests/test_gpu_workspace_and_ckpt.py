@@ -121,18 +121,29 @@ def test_flat_adam_state_dict_is_torch_adams(use_deform):
         assert torch.allclose(ref[i]["exp_avg_sq"], sd["state"][i]["exp_avg_sq"], rtol=1e-4, atol=1e-12)
 
 
-@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs in one process")
 def test_two_renderers_on_two_devices_in_one_process():
-    """Per-device constant tables / kernel attributes and per-device streams."""
+    """Per-device constant tables / kernel attributes and per-device streams: a second renderer in the same process,
+    on the second GPU where there is one, gives the first one's result and leaves the first one's state alone.  On a one-GPU box the
+    second renderer shares device 0 -- two engines on one slot of the library's device table, initialised once -- and in both cases it
+    runs on a stream of its own, so the library must launch on the stream of the engine that calls it."""
+    second = torch.device("cuda", 1 if torch.cuda.device_count() >= 2 else 0)
     r0 = renderer_for(41, "trained", True)
     from endosurf_amd import EndoSurfRenderer
     from gpu_util import net_cfg, state_to_ckpt
     from oracle_util import RENDER_CFG
     import weightgen
-    r1 = EndoSurfRenderer(dict(RENDER_CFG), net_cfg(True), device="cuda:1")
+    r1 = EndoSurfRenderer(dict(RENDER_CFG), net_cfg(True), device=second)
     r1.load_checkpoint(state_to_ckpt(weightgen.make_state(41, "trained", True), True))
+    assert r1.engine is not r0.engine and r1.engine.device == second
     rays = _batch(128)["rays"]
+    rays1 = rays.to(second)
+    side = torch.cuda.Stream(device=second)
+    side.wait_stream(torch.cuda.current_stream(second))          # r1's weights and rays1 were written on that device's default stream
     with torch.no_grad():
         a = r0(rays, iter_step=1, perturb_overwrite=False)["color_map"]
-        b = r1(rays.to("cuda:1"), iter_step=1, perturb_overwrite=False)["color_map"]
+        with torch.cuda.stream(side):
+            b = r1(rays1, iter_step=1, perturb_overwrite=False)["color_map"]
+        a2 = r0(rays, iter_step=1, perturb_overwrite=False)["color_map"]          # (issued while r1's launches may still be running)
+    side.synchronize()
     assert torch.allclose(a.cpu(), b.cpu(), atol=1e-6)
+    assert torch.allclose(a, a2, atol=1e-6)

@@ -209,6 +209,32 @@ def test_bench_work_model_and_self_launch(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_dump_outputs_names_and_size_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (Workload.dump_outputs on a stand-in workload): a training step's loss, terms, render dictionary and updated
+    parameters by name as float32 .npy files; when the arrays exceed the budget, the large ones are written as the SAME sample every time."""
+    import os
+    from types import SimpleNamespace
+    import bench
+    wl = SimpleNamespace(mode="train", renderer=SimpleNamespace(model=SimpleNamespace(_flat=torch.arange(10.0))))
+    ret = dict(color_map=torch.rand(64, 3), s_val=torch.rand(1, 1).expand(64, 1), gradient_o_error=torch.tensor(0.5, requires_grad=True),
+               weights=torch.rand(64, 1000, dtype=torch.float64))
+    out = (torch.tensor(1.5), dict(color=torch.tensor(0.25)), ret)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100000)
+    for d in ("a", "b"):
+        bench.Workload.dump_outputs(wl, out, str(tmp_path / d))
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"loss", "loss_color", "color_map", "s_val", "gradient_o_error", "weights", "params"}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 100000
+    assert got["params"].shape == (10,) and float(got["loss"]) == 1.5 and np.array_equal(got["color_map"], ret["color_map"].numpy()) and got["s_val"].shape == (64, 1)
+    w = got["weights"]          # 64 000 elements against 100 000 / 7 bytes per array: a sample, in the array's own order
+    assert w.ndim == 1 and 3000 < w.size < 64000 and np.isin(w, ret["weights"].float().numpy()).all()
+    assert np.array_equal(w, np.load(tmp_path / "b" / "weights.npy"))
+    # forward / frame: the step's dictionary as it is
+    bench.Workload.dump_outputs(SimpleNamespace(mode="frame"), dict(color=torch.zeros(8, 3), depth=torch.ones(8, 1)), str(tmp_path / "f"))
+    assert sorted(os.listdir(tmp_path / "f")) == ["color.npy", "depth.npy"]
+
+
 def test_workspace_budget_chunking_arithmetic():
     """_chunk_rays: rays per chunk of a grad-enabled render under render_cfg["workspace_gb"] (host arithmetic over the C layout query)."""
     from types import SimpleNamespace

@@ -2,7 +2,7 @@
 # The other bench.py lines of a round (GPU box):  bash tools/bench_configs.sh <tag>
 #   profiles/<tag>_cfg3.json / _cfg4.json / _cfg5_frame.json / _forward.json  and the OPT-IN split-precision lines _split.json / _forward_split.json / _cfg5_frame_split.json
 TAG=$1
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 cd $R
 mkdir -p profiles gpurun_out
 python bench.py --config 3 --steps 15 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > profiles/${TAG}_cfg3.json

@@ -8,7 +8,7 @@
 #   <tag>_plain_bench.json         its record (ms per step, host issue, library calls per step)
 set -u
 TAG=$1
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O $R/profiles
 cd /tmp && export TMPDIR=/tmp
