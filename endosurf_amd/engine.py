@@ -11,10 +11,34 @@ from . import _lib
 from ._lib import check, es_composite_args, es_points, ptr, stream_ptr
 
 
-def _f32(t: torch.Tensor) -> torch.Tensor:
-    if t.dtype != torch.float32 or not t.is_contiguous():
-        t = t.to(torch.float32).contiguous()
-    return t
+def f32(t: torch.Tensor) -> torch.Tensor:
+    """``t`` as the library reads it: detached, fp32, contiguous (no copy when it already is fp32 and contiguous)."""
+    return t.detach().to(torch.float32).contiguous()
+
+
+def u8(valid: torch.Tensor) -> torch.Tensor:
+    """A per-ray validity mask as the bytes the library reads (a bool tensor is reinterpreted, not converted)."""
+    return (valid.view(torch.uint8) if valid.dtype == torch.bool else valid.to(torch.uint8)).contiguous()
+
+
+class PointCtx:
+    """Workspace of one fused point evaluation + typed views of its outputs."""
+    _OUT = {"xc": (_lib.WS_XC, 3), "v": (_lib.WS_V, 3), "sdf": (_lib.WS_SDF, 1), "feat": (_lib.WS_FEAT, 256),
+            "gc": (_lib.WS_GC, 3), "go": (_lib.WS_GO, 3), "rgb": (_lib.WS_RGB, 3), "curv": (_lib.WS_CURV, 3), "xcbar": (_lib.WS_XCBAR, 3),
+            "tbar": (_lib.WS_TBAR, 1), "vbar": (_lib.WS_VBAR, 3)}
+
+    def __init__(self, eng: "Engine", pts, flags: int, m_color: int = 0):
+        self.eng, self.pts, self.flags, self.M, self.m_color = eng, pts, flags, pts.M, int(m_color)
+        self.x3_chain, self.px3 = False, None      # set by Engine.point_forward when the split-precision training chain produced it
+        self.Mp = (self.M + 127) // 128 * 128        # csrc/workspace.h round_up_rows
+        n = int(eng.lib.es_point_workspace_floats(self.M, flags))
+        self.ws = eng.empty(max(n, 1))
+
+    def view(self, name):
+        buf, width = self._OUT[name]
+        off = int(self.eng.lib.es_point_workspace_offset(self.M, self.flags, buf))
+        v = self.ws[off:off + self.Mp * width].view(self.Mp, width)[:self.M]
+        return v
 
 
 class Engine:
@@ -109,7 +133,7 @@ class Engine:
             if torch.cuda.is_current_stream_capturing():
                 raise _lib.EndoSurfHipError("the step arena must exist before a step is captured (run one eager step first)")
             self._arena = self.empty(need)
-        check(self.lib.es_zero(ptr(self._arena), 4 * self._arena.numel(), self.st()), "es_zero")
+        self.zero(self._arena)
         self._arena_off, self._arena_on = 0, True
         self._rng_step_calls = 0
 
@@ -146,7 +170,7 @@ class Engine:
         weff = self.empty(self.n_weff)
         packed = self.empty(self.n_packed)
         if not use_deform:
-            check(self.lib.es_zero(ptr(weff), 4 * weff.numel(), self.st()), "es_zero")
+            self.zero(weff)
         check(self.lib.es_weightnorm_pack(ptr(flat_params), ptr(weff), ptr(packed), int(use_deform), self.st()), "es_weightnorm_pack")
         return weff, packed
 
@@ -280,12 +304,11 @@ class Engine:
         src = self.empty(N, S, dtype=torch.int32)
         z_new = self.empty(N, n_imp)
         for i in range(up_sample_steps):
-            check(self.lib.es_upsample_step(ptr(rays), ptr(zc), S, ptr(sdf_c), ld_sdf, N, n, n_imp, float(64 * 2 ** i), ptr(z_new),
-                                            ptr(zn), S, ptr(src), self.st()), "es_upsample_step")
+            self.upsample_step(rays, zc, S, sdf_c, ld_sdf, N, n, n_imp, 64 * 2 ** i, z_new, zn, S, src)
             if i + 1 != up_sample_steps:
                 sdf_new = self.query_sdf(self.points(rays=rays, z=z_new, n_per_ray=n_imp, ldz=n_imp), weff, packed, use_deform)
                 dst = sdf_a if sdf_c.data_ptr() != sdf_a.data_ptr() else sdf_b
-                check(self.lib.es_merge_sdf(ptr(sdf_c), ld_sdf, ptr(sdf_new), n_imp, ptr(src), S, N, n, ptr(dst), self.st()), "es_merge_sdf")
+                self.merge_sdf(sdf_c, ld_sdf, sdf_new, n_imp, src, S, N, n, dst)
                 sdf_c, ld_sdf = dst, S
             zc, zn = zn, zc
             n += n_imp
@@ -358,7 +381,7 @@ class Engine:
     def variance_terms(self, variance, d_invs_acc=None):
         """SingleVarianceNetwork's scalar epilogue: s_val = 1 / inv_s, or (with ``d_invs_acc``) the gradient of the variance."""
         out = self.empty(1)
-        v = _f32(variance).reshape(1)
+        v = f32(variance).reshape(1)
         if d_invs_acc is None:
             check(self.lib.es_variance_terms(ptr(v), None, ptr(out), None, self.st()), "es_variance_terms")
         else:
@@ -402,15 +425,14 @@ class Engine:
     def march_refine(self, ms, n_secant_steps=8):
         """Second half (endosurf.py:410-449): n_secant_steps dependent secant iterations (latency-bound small launches)."""
         rays, N = ms["rays"], ms["rays"].shape[0]
-        st = self.st()
         x = self.empty(N, 3)
         t = self.empty(N)
         for _ in range(n_secant_steps):
-            check(self.lib.es_secant_points(ptr(rays), ptr(ms["d_pred"]), N, ptr(x), ptr(t), st), "es_secant_points")
+            self.secant_points(rays, ms["d_pred"], N, x, t)
             f_mid = self.query_sdf(self.points(x=x, t=t), ms["weff"], ms["packed"], ms["use_deform"])
-            check(self.lib.es_secant_update(ptr(f_mid), N, ms["tau"], ptr(ms["state"]), ptr(ms["d_pred"]), st), "es_secant_update")
+            self.secant_update(f_mid, N, ms["tau"], ms["state"], ms["d_pred"])
         d_out = self.empty(N, 1)
-        check(self.lib.es_march_finish(ptr(ms["d_pred"]), ptr(ms["flags"]), N, ptr(d_out), st), "es_march_finish")
+        check(self.lib.es_march_finish(ptr(ms["d_pred"]), ptr(ms["flags"]), N, ptr(d_out), self.st()), "es_march_finish")
         return d_out
 
     def ray_marching(self, rays, weff, packed, use_deform, n_steps=128, n_secant_steps=8, tau=0.0):
@@ -427,144 +449,163 @@ class Engine:
             return d_out
         return self.march_refine(self.march_begin(rays, weff, packed, use_deform, n_steps, tau), n_secant_steps)
 
+    # ---- fused point evaluation --------------------------------------------------------------------
+    def point_forward(self, pts, weff, packed, flags: int, m_color: int = 0, fp32_only: bool = False) -> PointCtx:
+        """``fp32_only``: keep the evaluation on the fp32 kernels in split-precision mode too (the point adjoint reads their mask words)."""
+        ctx = PointCtx(self, pts, flags, m_color)
+        save = bool(flags & _lib.PF_SAVE)
+        if self.split_precision and pts.M >= self.x3_infer_min and (self.x3_train_chain or not save) and not fp32_only:
+            # opt-in: the launches of a large evaluation in split precision -- csrc/infer_x3r.hip without PF_SAVE; with PF_SAVE the
+            # split-precision TRAINING chain, whose workspace must go through es_point_backward_x3 (``ctx.x3_chain``)
+            px3 = self.packed_x3(weff, bool(flags & _lib.PF_DEFORM))
+            check(self.lib.es_point_forward_x3(C.byref(pts), ptr(packed), ptr(px3), ptr(weff), ptr(ctx.ws), flags, int(m_color),
+                                               self.st()), "es_point_forward_x3")
+            ctx.x3_chain = save
+            ctx.px3 = px3
+        else:
+            check(self.lib.es_point_forward(C.byref(pts), ptr(packed), ptr(weff), ptr(ctx.ws), flags, int(m_color), self.st()), "es_point_forward")
+        return ctx
 
-class PointCtx:
-    """Workspace of one fused point evaluation + typed views of its outputs."""
-    _OUT = {"xc": (_lib.WS_XC, 3), "v": (_lib.WS_V, 3), "sdf": (_lib.WS_SDF, 1), "feat": (_lib.WS_FEAT, 256),
-            "gc": (_lib.WS_GC, 3), "go": (_lib.WS_GO, 3), "rgb": (_lib.WS_RGB, 3), "curv": (_lib.WS_CURV, 3), "xcbar": (_lib.WS_XCBAR, 3),
-            "tbar": (_lib.WS_TBAR, 1), "vbar": (_lib.WS_VBAR, 3)}
+    def point_forward_rows(self, ctx: PointCtx, weff, packed, row0: int, nrows: int):
+        """Rows [row0, row0 + nrows) of a workspace that is filled piece by piece (es_point_forward_rows): the colour part of a render whose
+        workspace has room for the colour-less points of later calls, or one of those calls' pieces of the tail.  fp32 kernels."""
+        check(self.lib.es_point_forward_rows(C.byref(ctx.pts), ptr(packed), ptr(weff), ptr(ctx.ws), ctx.flags, ctx.m_color, int(row0), int(nrows),
+                                             self.st()), "es_point_forward_rows")
 
-    def __init__(self, eng: "Engine", pts, flags: int, m_color: int = 0):
-        self.eng, self.pts, self.flags, self.M, self.m_color = eng, pts, flags, pts.M, int(m_color)
-        self.x3_chain, self.px3 = False, None      # set by Engine.point_forward when the split-precision training chain produced it
-        self.Mp = (self.M + 127) // 128 * 128        # csrc/workspace.h round_up_rows
-        n = int(eng.lib.es_point_workspace_floats(self.M, flags))
-        self.ws = eng.empty(max(n, 1))
-
-    def view(self, name):
-        buf, width = self._OUT[name]
-        off = int(self.eng.lib.es_point_workspace_offset(self.M, self.flags, buf))
-        v = self.ws[off:off + self.Mp * width].view(self.Mp, width)[:self.M]
-        return v
-
-
-def _point_forward(self, pts, weff, packed, flags: int, m_color: int = 0, fp32_only: bool = False) -> PointCtx:
-    """``fp32_only``: keep the evaluation on the fp32 kernels in split-precision mode too (the point adjoint reads their mask words)."""
-    ctx = PointCtx(self, pts, flags, m_color)
-    save = bool(flags & _lib.PF_SAVE)
-    if self.split_precision and pts.M >= self.x3_infer_min and (self.x3_train_chain or not save) and not fp32_only:
-        # opt-in: the launches of a large evaluation in split precision -- csrc/infer_x3r.hip without PF_SAVE; with PF_SAVE the
-        # split-precision TRAINING chain, whose workspace must go through es_point_backward_x3 (``ctx.x3_chain``)
-        px3 = self.packed_x3(weff, bool(flags & _lib.PF_DEFORM))
-        check(self.lib.es_point_forward_x3(C.byref(pts), ptr(packed), ptr(px3), ptr(weff), ptr(ctx.ws), flags, int(m_color),
-                                           self.st()), "es_point_forward_x3")
-        ctx.x3_chain = save
-        ctx.px3 = px3
-    else:
-        check(self.lib.es_point_forward(C.byref(pts), ptr(packed), ptr(weff), ptr(ctx.ws), flags, int(m_color), self.st()), "es_point_forward")
-    return ctx
-
-
-Engine.point_forward = _point_forward
-
-
-def _point_forward_rows(self, ctx: PointCtx, weff, packed, row0: int, nrows: int):
-    """Rows [row0, row0 + nrows) of a workspace that is filled piece by piece (es_point_forward_rows): the colour part of a render whose
-    workspace has room for the colour-less points of later calls, or one of those calls' pieces of the tail.  fp32 kernels."""
-    check(self.lib.es_point_forward_rows(C.byref(ctx.pts), ptr(packed), ptr(weff), ptr(ctx.ws), ctx.flags, ctx.m_color, int(row0), int(nrows),
-                                         self.st()), "es_point_forward_rows")
-
-
-Engine.point_forward_rows = _point_forward_rows
-
-
-def _point_backward(self, ctx: PointCtx, weff, packed, d_sdf, d_go, d_rgb=None, dweff=None, staged: bool = False):
-    """Adjoints of (sdf [M,1], g_o [M,3], rgb [M,3]) -> gradient w.r.t. the effective-weight buffer (accumulated into
-    ``dweff`` if given).  ``staged``: this call produces the WHOLE gradient of a step (not one chunk of several), so
-    ``engine.wgrad_stage_hook(stage, dweff)`` -- if set -- may be called behind every network's weight-gradient launch."""
-    M = ctx.M
-    z = lambda g, w: (g.detach().to(torch.float32).contiguous() if g is not None else self.zeros(M, w))
-    d_sdf, d_go = z(d_sdf, 1), z(d_go, 3)
-    color = bool(ctx.flags & _lib.PF_COLOR)
-    if color:
-        mc = ctx.m_color if ctx.m_color > 0 else M
-        d_rgb = d_rgb.detach().to(torch.float32).contiguous() if d_rgb is not None else self.zeros(mc, 3)
-        assert d_rgb.shape[0] == mc
-    if dweff is None:
-        dweff = self.zeros(self.n_weff)
-        if self._grad_pipeline is not None:          # a pipelined data-parallel step counts the gradient buffers of its weff consumers
-            self._grad_pipeline["buffers"] = self._grad_pipeline.get("buffers", 0) + 1
-    if ctx.x3_chain:      # the workspace of the split-precision training chain: that family's backward kernels
-        check(self.lib.es_point_backward_x3(C.byref(ctx.pts), ptr(packed), ptr(ctx.px3), ptr(weff), ptr(ctx.ws), ctx.flags, ctx.m_color, ptr(d_sdf),
-                                            ptr(d_go), ptr(d_rgb) if color else None, ptr(dweff), ptr(self.wg_scratch()), self.st()),
-              "es_point_backward_x3")
+    def point_backward(self, ctx: PointCtx, weff, packed, d_sdf, d_go, d_rgb=None, dweff=None, staged: bool = False):
+        """Adjoints of (sdf [M,1], g_o [M,3], rgb [M,3]) -> gradient w.r.t. the effective-weight buffer (accumulated into
+        ``dweff`` if given).  ``staged``: this call produces the WHOLE gradient of a step (not one chunk of several), so
+        ``engine.wgrad_stage_hook(stage, dweff)`` -- if set -- may be called behind every network's weight-gradient launch."""
+        M = ctx.M
+        z = lambda g, w: (f32(g) if g is not None else self.zeros(M, w))
+        d_sdf, d_go = z(d_sdf, 1), z(d_go, 3)
+        color = bool(ctx.flags & _lib.PF_COLOR)
+        if color:
+            mc = ctx.m_color if ctx.m_color > 0 else M
+            d_rgb = f32(d_rgb) if d_rgb is not None else self.zeros(mc, 3)
+            assert d_rgb.shape[0] == mc
+        if dweff is None:
+            dweff = self.zeros(self.n_weff)
+            if self._grad_pipeline is not None:          # a pipelined data-parallel step counts the gradient buffers of its weff consumers
+                self._grad_pipeline["buffers"] = self._grad_pipeline.get("buffers", 0) + 1
+        if ctx.x3_chain:      # the workspace of the split-precision training chain: that family's backward kernels
+            check(self.lib.es_point_backward_x3(C.byref(ctx.pts), ptr(packed), ptr(ctx.px3), ptr(weff), ptr(ctx.ws), ctx.flags, ctx.m_color, ptr(d_sdf),
+                                                ptr(d_go), ptr(d_rgb) if color else None, ptr(dweff), ptr(self.wg_scratch()), self.st()),
+                  "es_point_backward_x3")
+            return dweff
+        flags = ctx.flags | (_lib.PF_X3 if self.split_precision else 0)      # opt-in: weight-gradient GEMMs in split precision
+        hook = self.wgrad_stage_hook if staged else None
+        if hook is not None:
+            # the same launches in four calls, with the caller's hook between them: a data-parallel trainer starts the all-reduce of a
+            # network's gradient while the next network's weight-gradient launch runs (Trainer(overlap_allreduce=True))
+            for stage in (_lib.BWD_CHAINS, _lib.BWD_WGRAD_DEFORM, _lib.BWD_WGRAD_SDF, _lib.BWD_WGRAD_COLOR):
+                check(self.lib.es_point_backward_stages(C.byref(ctx.pts), ptr(packed), ptr(weff), ptr(ctx.ws), flags, ctx.m_color, ptr(d_sdf), ptr(d_go),
+                                                        ptr(d_rgb) if color else None, ptr(dweff), ptr(self.wg_scratch()), stage, self.st()),
+                      "es_point_backward_stages")
+                if stage != _lib.BWD_CHAINS:
+                    hook(stage, dweff)
+            return dweff
+        check(self.lib.es_point_backward_det(C.byref(ctx.pts), ptr(packed), ptr(weff), ptr(ctx.ws), flags, ctx.m_color, ptr(d_sdf), ptr(d_go),
+                                             ptr(d_rgb) if color else None, ptr(dweff), ptr(self.wg_scratch()), self.st()), "es_point_backward")
         return dweff
-    flags = ctx.flags | (_lib.PF_X3 if self.split_precision else 0)      # opt-in: weight-gradient GEMMs in split precision
-    hook = self.wgrad_stage_hook if staged else None
-    if hook is not None:
-        # the same launches in four calls, with the caller's hook between them: a data-parallel trainer starts the all-reduce of a
-        # network's gradient while the next network's weight-gradient launch runs (Trainer(overlap_allreduce=True))
-        for stage in (_lib.BWD_CHAINS, _lib.BWD_WGRAD_DEFORM, _lib.BWD_WGRAD_SDF, _lib.BWD_WGRAD_COLOR):
-            check(self.lib.es_point_backward_stages(C.byref(ctx.pts), ptr(packed), ptr(weff), ptr(ctx.ws), flags, ctx.m_color, ptr(d_sdf), ptr(d_go),
-                                                    ptr(d_rgb) if color else None, ptr(dweff), ptr(self.wg_scratch()), stage, self.st()),
-                  "es_point_backward_stages")
-            if stage != _lib.BWD_CHAINS:
-                hook(stage, dweff)
-        return dweff
-    check(self.lib.es_point_backward_det(C.byref(ctx.pts), ptr(packed), ptr(weff), ptr(ctx.ws), flags, ctx.m_color, ptr(d_sdf), ptr(d_go),
-                                         ptr(d_rgb) if color else None, ptr(dweff), ptr(self.wg_scratch()), self.st()), "es_point_backward")
-    return dweff
 
+    def point_input_adjoint(self, ctx: PointCtx, weff, packed, d_sdf, d_go):
+        """The adjoint of the QUERY POINTS through g_o (and only through g_o: callers that expose sdf as a function of the points attach
+        d sdf / d x = g_o themselves, model.EndoSurfNet.get_sdf_from_observed_space) -- the reference's create_graph=True second
+        derivative (endosurf.py:581-601, :603-619).  Call right after point_backward on the same context:
+            xbar = J^T xcbar - d_go * curv(g_c) - d_sdf * g_o        (include/endosurf_hip.h es_point_vjp; without a deformation network J = I)
+        where xcbar (the backward's adjoint of x_c) carries the Hessian-vector product of the SDF network along J d_go, the curvature term is
+        the deformation network's own second derivative, and the last term removes the sdf path's share of xcbar.  Overwrites the
+        workspace's g_c / g_o / curvature buffers."""
+        M = ctx.M
+        if ctx.x3_chain:
+            raise _lib.EndoSurfHipError("the point adjoint needs a workspace of the fp32 kernels (point_forward(..., fp32_only=True))")
+        xcbar = ctx.view("xcbar")
+        go = ctx.view("go").clone()
+        if ctx.flags & _lib.PF_DEFORM:
+            curv = ctx.view("curv").clone()
+            ctx.view("gc").copy_(xcbar)
+            self.point_vjp(ctx, weff, packed)
+            xbar = ctx.view("go").clone()
+            if d_go is not None:
+                xbar -= d_go.detach().to(torch.float32).reshape(M, 3) * curv
+        else:
+            xbar = xcbar.clone()
+        if d_sdf is not None:
+            xbar -= d_sdf.detach().to(torch.float32).reshape(M, 1) * go
+        return xbar
 
-Engine.point_backward = _point_backward
+    # ---- single launches ----------------------------------------------------------------------------
+    # One method per library entry point that the renderer, its autograd functions and the trainer call: the pointer marshalling and the
+    # status check, nothing else (tensors or None in; the caller allocates, converts and owns every buffer).  Arguments in the order of
+    # include/endosurf_hip.h, which documents them -- except that ``weff`` comes before ``packed``, as everywhere in this class.
+    def copy2(self, dst_a, src_a, n_a, dst_b, src_b, n_b):
+        check(self.lib.es_copy2(ptr(dst_a), ptr(src_a), int(n_a), ptr(dst_b), ptr(src_b), int(n_b), self.st()), "es_copy2")
+    def zero(self, buf):
+        check(self.lib.es_zero(ptr(buf), 4 * buf.numel(), self.st()), "es_zero")
+    def scale(self, out, src, n, factor_dev):
+        check(self.lib.es_scale(ptr(out), ptr(src), int(n), ptr(factor_dev), self.st()), "es_scale")
 
-
-def _point_input_adjoint(self, ctx: PointCtx, weff, packed, d_sdf, d_go):
-    """The adjoint of the QUERY POINTS through g_o (and only through g_o: callers that expose sdf as a function of the points attach
-    d sdf / d x = g_o themselves, renderer.EndoSurfNet.get_sdf_from_observed_space) -- the reference's create_graph=True second
-    derivative (endosurf.py:581-601, :603-619).  Call right after point_backward on the same context:
-        xbar = J^T xcbar - d_go * curv(g_c) - d_sdf * g_o        (include/endosurf_hip.h es_point_vjp; without a deformation network J = I)
-    where xcbar (the backward's adjoint of x_c) carries the Hessian-vector product of the SDF network along J d_go, the curvature term is
-    the deformation network's own second derivative, and the last term removes the sdf path's share of xcbar.  Overwrites the
-    workspace's g_c / g_o / curvature buffers."""
-    M = ctx.M
-    if ctx.x3_chain:
-        raise _lib.EndoSurfHipError("the point adjoint needs a workspace of the fp32 kernels (point_forward(..., fp32_only=True))")
-    xcbar = ctx.view("xcbar")
-    go = ctx.view("go").clone()
-    if ctx.flags & _lib.PF_DEFORM:
-        curv = ctx.view("curv").clone()
-        ctx.view("gc").copy_(xcbar)
+    def color_forward(self, ctx: PointCtx, weff, packed):
+        check(self.lib.es_color_forward(C.byref(ctx.pts), ptr(packed), ptr(weff), ptr(ctx.ws), self.st()), "es_color_forward")
+    def point_vjp(self, ctx: PointCtx, weff, packed):
         check(self.lib.es_point_vjp(C.byref(ctx.pts), ptr(packed), ptr(weff), ptr(ctx.ws), ctx.flags, self.st()), "es_point_vjp")
-        xbar = ctx.view("go").clone()
-        if d_go is not None:
-            xbar -= d_go.detach().to(torch.float32).reshape(M, 3) * curv
-    else:
-        xbar = xcbar.clone()
-    if d_sdf is not None:
-        xbar -= d_sdf.detach().to(torch.float32).reshape(M, 1) * go
-    return xbar
+    def render_finish(self, eik_acc, aux_sdf_src, aux_go_src, n_aux, eik, den2, aux_sdf, aux_go):
+        check(self.lib.es_render_finish(ptr(eik_acc), ptr(aux_sdf_src), ptr(aux_go_src), int(n_aux), ptr(eik), ptr(den2), ptr(aux_sdf), ptr(aux_go),
+                                        self.st()), "es_render_finish")
 
+    def upsample_step(self, rays, z, ldz, sdf, ld_sdf, N, n, n_imp, inv_s, z_new, z_out, ld_out, src):
+        check(self.lib.es_upsample_step(ptr(rays), ptr(z), ldz, ptr(sdf), ld_sdf, N, n, n_imp, float(inv_s), ptr(z_new), ptr(z_out), ld_out, ptr(src),
+                                        self.st()), "es_upsample_step")
+    def merge_sdf(self, sdf, ld_sdf, sdf_new, n_new, src, ld_src, N, n, out):
+        check(self.lib.es_merge_sdf(ptr(sdf), ld_sdf, ptr(sdf_new), n_new, ptr(src), ld_src, N, n, ptr(out), self.st()), "es_merge_sdf")
 
-Engine.point_input_adjoint = _point_input_adjoint
+    def secant_points(self, rays, d_pred, N, x, t):
+        check(self.lib.es_secant_points(ptr(rays), ptr(d_pred), N, ptr(x), ptr(t), self.st()), "es_secant_points")
+    def secant_update(self, f_mid, N, tau, state, d_pred):
+        check(self.lib.es_secant_update(ptr(f_mid), N, float(tau), ptr(state), ptr(d_pred), self.st()), "es_secant_update")
 
+    def eod_points(self, rays, d_gt, mask, N, x, t, inside):
+        check(self.lib.es_eod_points(ptr(rays), ptr(d_gt), ptr(mask), N, ptr(x), ptr(t), ptr(inside), self.st()), "es_eod_points")
+    def eod_loss(self, rays, pts, mask, sdf, go, N, out, inside):
+        check(self.lib.es_eod_loss(ptr(rays), ptr(pts), ptr(mask), ptr(sdf), ptr(go), N, ptr(out), ptr(inside), self.st()), "es_eod_loss")
+    def eod_loss_backward(self, rays, inside, sdf, go, out, g_sdf_err, g_ang_err, N, d_sdf, d_go):
+        check(self.lib.es_eod_loss_backward(ptr(rays), ptr(inside), ptr(sdf), ptr(go), ptr(out), ptr(g_sdf_err), ptr(g_ang_err), N, ptr(d_sdf),
+                                            ptr(d_go), self.st()), "es_eod_loss_backward")
+    def sn_points(self, rays, mask, d_i, u, neighbour_rad, N, x, t, valid):
+        check(self.lib.es_sn_points(ptr(rays), ptr(mask), ptr(d_i), ptr(u), float(neighbour_rad), N, ptr(x), ptr(t), ptr(valid), self.st()), "es_sn_points")
+    def sn_loss(self, g, valid8, N, out):
+        check(self.lib.es_sn_loss(ptr(g), ptr(valid8), N, ptr(out), self.st()), "es_sn_loss")
+    def sn_loss_backward(self, g, valid8, out, g_loss, N, d_g):
+        check(self.lib.es_sn_loss_backward(ptr(g), ptr(valid8), ptr(out), ptr(g_loss), N, ptr(d_g), self.st()), "es_sn_loss_backward")
 
+    def train_aux_points(self, rays, depth_gt, mask, d_i, u, neighbour_rad, N, x, t, valid):
+        check(self.lib.es_train_aux_points(ptr(rays), ptr(depth_gt), ptr(mask), ptr(d_i), ptr(u), float(neighbour_rad), N, ptr(x), ptr(t), ptr(valid),
+                                           self.st()), "es_train_aux_points")
+    def train_loss(self, args):          # a filled es_loss_args (trainer._LossFn)
+        check(self.lib.es_train_loss(C.byref(args), self.st()), "es_train_loss")
+    def train_schedule(self, state, lr_init, n_iter, warm_up_end, lr_alpha, beta1, beta2, grad_scale, anneal_end, scalars):
+        check(self.lib.es_train_schedule(ptr(state), float(lr_init), float(n_iter), float(warm_up_end), float(lr_alpha), float(beta1), float(beta2),
+                                         grad_scale, float(anneal_end), ptr(scalars), self.st()), "es_train_schedule")
+    def adam_step(self, flat, grad, exp_avg, exp_avg_sq, n, beta1, beta2, eps, step_size, bc2_sqrt, grad_scale, grad_var, var_off):
+        check(self.lib.es_adam_step(ptr(flat), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), n, beta1, beta2, eps, step_size, bc2_sqrt, float(grad_scale),
+                                    ptr(grad_var), var_off, self.st()), "es_adam_step")
+    def adam_step_dev(self, flat, grad, exp_avg, exp_avg_sq, n, beta1, beta2, eps, scalars_dev, grad_var, var_off):
+        check(self.lib.es_adam_step_dev(ptr(flat), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), n, beta1, beta2, eps, ptr(scalars_dev), ptr(grad_var),
+                                        var_off, self.st()), "es_adam_step_dev")
 
-def _timing_enable(self, on: bool):
-    self._timing_on = bool(on)          # (events cannot be recorded inside a captured graph: the renderer's captured forward stands down)
-    check(self.lib.es_timing_enable(int(on)), "es_timing_enable")
+    # ---- per-kernel timers (csrc/timing.hip) ---------------------------------------------------------
+    def timing_enable(self, on: bool):
+        self._timing_on = bool(on)          # (events cannot be recorded inside a captured graph: the renderer's captured forward stands down)
+        check(self.lib.es_timing_enable(int(on)), "es_timing_enable")
 
+    def timing_drain(self):
+        """[(kernel name, rows, ms)] of every launch recorded since the last drain."""
+        cap = 65536
+        kid = (C.c_int * cap)()
+        rows = (C.c_longlong * cap)()
+        ms = (C.c_float * cap)()
+        n = C.c_int()
+        check(self.lib.es_timing_drain(cap, kid, rows, ms, C.byref(n)), "es_timing_drain")
+        return [(self.lib.es_kernel_name(kid[i]).decode(), int(rows[i]), float(ms[i])) for i in range(n.value)]
 
-def _timing_drain(self):
-    """[(kernel name, rows, ms)] of every launch recorded since the last drain."""
-    cap = 65536
-    kid = (C.c_int * cap)()
-    rows = (C.c_longlong * cap)()
-    ms = (C.c_float * cap)()
-    n = C.c_int()
-    check(self.lib.es_timing_drain(cap, kid, rows, ms, C.byref(n)), "es_timing_drain")
-    return [(self.lib.es_kernel_name(kid[i]).decode(), int(rows[i]), float(ms[i])) for i in range(n.value)]
-
-
-Engine.timing_enable = _timing_enable
-Engine.timing_drain = _timing_drain

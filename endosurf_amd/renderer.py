@@ -5,48 +5,25 @@ Same constructor (``render_cfg``, ``net_cfg``, ``device``), same public methods 
 ``state_dict`` key names (``model.{deform,sdf,color}_network.net.{l}.{bias,weight_g,weight_v}``,
 ``model.deviation_network.variance``) so reference checkpoints load unchanged.  Host code is orchestration only:
 every tensor op of the hot path runs inside the C-ABI library; there is no PyTorch/CPU fallback.
+
+The parameter container and the reference-named modules live in ``model``, the autograd functions in ``functions``, the rows a
+render keeps for the calls that follow it in ``tail``; this module is the renderer itself and the policy of its tail.
 """
 from __future__ import annotations
 
 import functools
-import math
 import os
 import weakref
-from typing import Dict, Optional
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, params as P
-from .engine import Engine, PointCtx
-
-# architecture every reference EndoSurf config uses (configs/endosurf/**: only ``use_deform`` varies)
-_ARCH = {
-    "deform_network": dict(n_layers=9, hidden_dim=256, skips=[4], out_dim=3,
-                           enc_pos_cfg=dict(enc_type="frequency", input_dim=3, multires=6),
-                           enc_time_cfg=dict(enc_type="frequency", input_dim=1, multires=6)),
-    "sdf_network": dict(n_layers=9, hidden_dim=256, skips=[4], out_dim=257,
-                        enc_pos_cfg=dict(enc_type="frequency", input_dim=3, multires=6)),
-    "color_network": dict(n_layers=9, hidden_dim=256, skips=[4], out_dim=3, feat_dim=256,
-                          enc_pos_cfg=dict(enc_type="frequency", input_dim=3, multires=10),
-                          enc_dir_cfg=dict(enc_type="frequency", input_dim=3, multires=4)),
-}
-
-
-def _check_arch(net_cfg: dict):
-    """The kernels are specialised for the one architecture the reference ships; anything else fails loudly."""
-    for net, want in _ARCH.items():
-        if net == "deform_network" and not net_cfg.get("use_deform", True):
-            continue
-        got = net_cfg[net]
-        for k, v in want.items():
-            g = got.get(k, v)
-            if isinstance(v, dict):
-                g = {kk: g.get(kk) for kk in v}
-            if g != v:
-                raise NotImplementedError(
-                    f"endosurf_amd kernels are specialised for net.{net}.{k} = {v!r} (all reference EndoSurf configs); got {g!r}")
+from . import _lib
+from .engine import Engine, f32
+from .functions import _EodLossFn, _PackFn, _PointEvalFn, _RenderFn, _SnLossFn, _SValFn
+from .model import EndoSurfNet, WNLinear, _check_arch, _reference_style_init  # noqa: F401  (the last two: importable from here as before)
+from .tail import _Lazy, _LazyEodFn, _PendingEod, _Tail, _TailEvalFn
 
 
 def _on_device(fn):
@@ -59,896 +36,6 @@ def _on_device(fn):
         with torch.cuda.device(self.device):
             return fn(self, *a, **k)
     return wrapped
-
-
-# ---------------------------------------------------------------------------------------------------------------
-# parameter holders (views into one flat fp32 device buffer whose layout is owned by csrc/arch.h)
-# ---------------------------------------------------------------------------------------------------------------
-class WNLinear(nn.Module):
-    """Parameters of one weight-normed nn.Linear, reference names/shapes: bias[N], weight_g[N,1], weight_v[N,K]."""
-
-    def __init__(self, flat: torch.Tensor, lay: dict, prefix: str):
-        super().__init__()
-        for name in ("bias", "weight_g", "weight_v"):
-            off, shape = lay[f"{prefix}.{name}"]
-            n = int(np.prod(shape))
-            self.register_parameter(name, nn.Parameter(flat[off:off + n].view(shape)))
-
-    replaced = 0          # bumped when a registered parameter is assigned anew: EndoSurfNet drops its cached parameter walk
-
-    def __setattr__(self, name, value):
-        if name in ("bias", "weight_g", "weight_v") and name in self.__dict__.get("_parameters", {}):
-            WNLinear.replaced += 1
-        super().__setattr__(name, value)
-
-    def forward(self, x):
-        """One weight-normed linear layer on its own, y = x (g v / |v|_row)^T + b: what ``model.<net>.net[l](x)`` gives in the reference
-        (nn.utils.weight_norm(nn.Linear), utils.py:57-58 / :108-109).  Not part of the hot path -- the fused kernels evaluate whole
-        networks -- so this is plain torch arithmetic on the parameter views, differentiable like the reference's."""
-        v = self.weight_v
-        w = self.weight_g * v / torch.linalg.norm(v, dim=1, keepdim=True)
-        return torch.nn.functional.linear(x.to(v.dtype), w, self.bias)
-
-
-class _MLP(nn.Module):
-    def __init__(self, flat, lay, net_name):
-        super().__init__()
-        self.net = nn.ModuleList([WNLinear(flat, lay, f"{net_name}.net.{l}") for l in range(9)])
-        self._model = None          # weakref to the owning EndoSurfNet (set there): the forwards below run the fused kernels
-
-    def _ctx(self):
-        m = self._model() if self._model is not None else None
-        if m is None:
-            raise RuntimeError("this network is not attached to an EndoSurfNet / EndoSurfRenderer")
-        return m, m._r()
-
-
-class DeformNetwork(_MLP):
-    def forward(self, x, t):
-        """Displacement field delta x(x, t) [M,3] (reference DeformNetwork.forward, endosurf.py:724-738), no grad: x_c of the fused
-        point evaluation minus x."""
-        m, r = self._ctx()
-        with torch.cuda.device(r.device), torch.no_grad():
-            x, t = m._xt(x, t)
-            weff, packed = r._weights()
-            pctx = r.engine.point_forward(r.engine.points(x=x, t=t), weff.detach(), packed, _lib.PF_DEFORM)
-            return pctx.view("xc") - x
-
-
-class SDFNetwork(_MLP):
-    def forward(self, x):
-        """[sdf | 256 geometry features] [M,257] at CANONICAL points (reference SDFNetwork.forward, endosurf.py:773-786), no grad."""
-        m, r = self._ctx()
-        with torch.cuda.device(r.device), torch.no_grad():
-            x, t = m._xt(x, torch.zeros(1, device=x.device))
-            weff, packed = r._weights()
-            d = torch.zeros_like(x)
-            d[:, 2] = 1.0
-            pctx = r.engine.point_forward(r.engine.points(x=x, t=t, dirs=d), weff.detach(), packed, _lib.PF_COLOR)   # features need the colour path's buffers
-            return torch.cat([pctx.view("sdf"), pctx.view("feat")], -1)
-
-    def sdf(self, x):
-        """sdf [M,1] at canonical points (endosurf.py:788-791)."""
-        return self.forward(x)[..., :1]
-
-
-class ColorNetwork(_MLP):
-    def forward(self, x, n, d, geo_feat):
-        """sigmoid rgb [M,3] of the colour MLP on EXPLICIT inputs (reference ColorNetwork.forward, endosurf.py:828-842): position x
-        (encoded with L = 10), normal n (used as given), view direction d (encoded with L = 4, used as given: EndoSurfNet.forward
-        normalises J d before this call, :684-685) and the 256 geometry features.  One launch of the fused chain's colour body on a
-        workspace whose x_c / g_c / feature buffers hold the inputs (es_color_forward).  No grad, like the other per-network forwards."""
-        m, r = self._ctx()
-        with torch.cuda.device(r.device), torch.no_grad():
-            f = lambda a, w: a.detach().to(device=r.device, dtype=torch.float32).reshape(-1, w).contiguous()
-            x, n, d, feat = f(x, 3), f(n, 3), f(d, 3), f(geo_feat, 256)
-            M = x.shape[0]
-            if not (n.shape[0] == d.shape[0] == feat.shape[0] == M):
-                raise ValueError("x, n, d and geo_feat must hold one row per point")
-            if M == 0:
-                return torch.zeros(0, 3, device=r.device)
-            weff, packed = r._weights()
-            eng = r.engine
-            pts = eng.points(x=x, t=torch.zeros(1, device=r.device), dirs=d)
-            pctx = PointCtx(eng, pts, _lib.PF_COLOR)
-            pctx.view("xc").copy_(x); pctx.view("gc").copy_(n); pctx.view("feat").copy_(feat)
-            _lib.check(eng.lib.es_color_forward(_lib.C.byref(pts), _lib.ptr(packed), _lib.ptr(weff.detach()), _lib.ptr(pctx.ws), eng.st()),
-                       "es_color_forward")
-            return pctx.view("rgb").clone()
-
-
-class SingleVarianceNetwork(nn.Module):
-    def __init__(self, flat, lay):
-        super().__init__()
-        off, _ = lay["deviation_network.variance"]
-        self.register_parameter("variance", nn.Parameter(flat[off:off + 1].view(())))
-
-    def forward(self, x):
-        """inv_s broadcast to [len(x), 1] (endosurf.py:850-852); plain torch, differentiable w.r.t. the variance."""
-        return torch.ones([len(x), 1], device=self.variance.device) * torch.exp(self.variance * 10.0)
-
-
-def _reference_style_init(flat: torch.Tensor, lay: dict, net_cfg: dict):
-    """Same initial distributions (and, under the same torch seed, the same draws in the same order) as the reference:
-    build_mlp_idr / build_mlp_nerf (utils.py:11-111) -> nn.Linear default init, geometric init for the SDF network
-    (bias 0.8), then weight_norm's g = ||W||_row, v = W; SingleVarianceNetwork init_val (endosurf.py:845-848)."""
-    sdf_bias = float(net_cfg["sdf_network"].get("geometric_init_bias", 0.8))
-    geometric = bool(net_cfg["sdf_network"].get("geometric_init", True))
-    order = (["deform_network"] if net_cfg.get("use_deform", True) else []) + ["sdf_network", "color_network"]
-    with torch.no_grad():
-        for net in order:
-            for l in range(9):
-                _, (n_out, n_in) = lay[f"{net}.net.{l}.weight_v"]
-                lin = nn.Linear(n_in, n_out)
-                W, b = lin.weight.data, lin.bias.data
-                if net == "sdf_network" and geometric:
-                    in_dim = 39
-                    if l == 8:
-                        nn.init.normal_(W, mean=math.sqrt(math.pi) / math.sqrt(n_in), std=1e-4)
-                        nn.init.constant_(b, -sdf_bias)
-                    elif l == 0:
-                        nn.init.constant_(b, 0.0)
-                        nn.init.constant_(W[:, 3:], 0.0)
-                        nn.init.normal_(W[:, :3], 0.0, math.sqrt(2) / math.sqrt(n_out))
-                    elif l == 4:
-                        nn.init.constant_(b, 0.0)
-                        nn.init.normal_(W, 0.0, math.sqrt(2) / math.sqrt(n_out))
-                        nn.init.constant_(W[:, -(in_dim - 3):], 0.0)
-                    else:
-                        nn.init.constant_(b, 0.0)
-                        nn.init.normal_(W, 0.0, math.sqrt(2) / math.sqrt(n_out))
-                for name, val in (("bias", b), ("weight_g", W.norm(dim=1, keepdim=True)), ("weight_v", W)):
-                    off, shape = lay[f"{net}.net.{l}.{name}"]
-                    flat[off:off + val.numel()].copy_(val.reshape(-1))
-        off, _ = lay["deviation_network.variance"]
-        flat[off] = float(net_cfg["deviation_network"]["init_val"])
-
-
-class EndoSurfNet(nn.Module):
-    """Parameter container mirroring the reference EndoSurfNet (endosurf.py:524-568)."""
-
-    def __init__(self, net_cfg: dict, device):
-        super().__init__()
-        _check_arch(net_cfg)
-        self.bound = net_cfg["bound"]
-        self.use_deform = bool(net_cfg["use_deform"])
-        lay = P.layout()
-        n = int(_lib.load().es_param_floats())
-        flat_cpu = torch.zeros(n)
-        _reference_style_init(flat_cpu, lay, net_cfg)
-        self._flat = flat_cpu.to(device)
-        if self.use_deform:
-            self.deform_network = DeformNetwork(self._flat, lay, "deform_network")
-        self.sdf_network = SDFNetwork(self._flat, lay, "sdf_network")
-        self.color_network = ColorNetwork(self._flat, lay, "color_network")
-        self.deviation_network = SingleVarianceNetwork(self._flat, lay)
-        self._layout = lay
-        for net in ((self.deform_network,) if self.use_deform else ()) + (self.sdf_network, self.color_network):
-            net._model = weakref.ref(self)
-
-    def get_train_params(self):
-        out = {}
-        if self.use_deform:
-            out["deform_network"] = list(self.deform_network.parameters())
-        out["sdf_network"] = list(self.sdf_network.parameters())
-        out["color_network"] = list(self.color_network.parameters())
-        out["deviation_network"] = list(self.deviation_network.parameters())
-        return out
-
-    def load_checkpoints(self, ckpt):
-        if self.use_deform:
-            self.deform_network.load_state_dict(ckpt["deform_network"])
-        self.sdf_network.load_state_dict(ckpt["sdf_network"])
-        self.color_network.load_state_dict(ckpt["color_network"])
-        self.deviation_network.load_state_dict(ckpt["deviation_network"])
-
-    def save_checkpoint(self):
-        ckpt = {}
-        if self.use_deform:
-            ckpt["deform_network"] = self.deform_network.state_dict()
-        ckpt["sdf_network"] = self.sdf_network.state_dict()
-        ckpt["color_network"] = self.color_network.state_dict()
-        ckpt["deviation_network"] = self.deviation_network.state_dict()
-        return ckpt
-
-    def ordered_params(self):
-        """(key, Parameter) in flat-buffer order, variance excluded.  (Built once: the modules and the identity of their Parameters are
-        fixed for the life of the model -- ``_rebind`` / ``_apply`` only re-point ``.data`` -- and the renderer's ``_weights()`` walks this
-        list several times per call of every public method.)"""
-        cached = self.__dict__.get("_ordered")
-        if cached is not None and self.__dict__.get("_ordered_at") == WNLinear.replaced:
-            return list(cached)
-        out = []
-        for net in P.NET_NAMES:
-            if net == "deform_network" and not self.use_deform:
-                continue
-            mod = getattr(self, net)
-            for l in range(9):
-                for name in ("bias", "weight_g", "weight_v"):
-                    out.append((f"{net}.net.{l}.{name}", getattr(mod.net[l], name)))
-        self.__dict__["_ordered"] = tuple(out)
-        self.__dict__["_ordered_at"] = WNLinear.replaced
-        self.__dict__["_plist"] = tuple(p for _, p in out)
-        var = self.deviation_network.variance
-        base = self._layout
-        self.__dict__["_view_slots"] = tuple((p, 4 * base[k][0]) for k, p in out) + ((var, 4 * base["deviation_network.variance"][0]),)
-        return out
-
-    # ---- flat-buffer binding -------------------------------------------------------------------------------------------
-    def _rebind(self):
-        """Point every nn.Parameter back at its slot of the flat buffer (Parameter identity is kept, so optimisers stay valid)."""
-        with torch.no_grad():
-            for key, p in self.ordered_params() + [("deviation_network.variance", self.deviation_network.variance)]:
-                off, shape = self._layout[key]
-                p.data = self._flat[off:off + max(1, int(np.prod(shape)))].view(tuple(shape))
-        self._pack_cache = None
-        self._epoch = getattr(self, "_epoch", 0) + 1
-
-    def _apply(self, fn, recurse=True):
-        """``.to() / .cuda() / .float()``: move the FLAT buffer and rebuild the parameter views (nn.Module._apply would give
-        every parameter its own storage and the kernels would keep reading the stale flat buffer)."""
-        new = fn(self._flat)
-        if new.dtype != torch.float32 or new.device.type != "cuda":
-            raise TypeError(f"endosurf_amd parameters live in one fp32 buffer on an AMD GPU (got {new.dtype} on {new.device}); "
-                            "the HIP kernels compute in fp32 only")
-        if new.device != self._flat.device:
-            raise RuntimeError(f"an EndoSurfRenderer is bound to the GPU it was constructed on ({self._flat.device}: engine, constant tables, "
-                               f"streams); construct a new one on {new.device} and load_checkpoint(save_checkpoint()) instead of .to()")
-        self._flat = new.contiguous()
-        self._rebind()
-        return self
-
-    def _check_views(self, spot: bool = False):
-        """Every parameter must still be a view of the flat buffer; anything that re-bound parameter storage (``p.data = ...``
-        loaders, DDP/FSDP flattening, ...) is folded back into it.  ``spot``: look at the first and the last tensor only (the renderer
-        does the full walk once per parameter version and this one at every other call)."""
-        base = self._flat.data_ptr()
-        slots = self.__dict__.get("_view_slots")
-        if slots is None or self.__dict__.get("_ordered_at") != WNLinear.replaced:
-            self.ordered_params()
-            slots = self.__dict__["_view_slots"]
-        if spot:
-            (p0, o0), (p1, o1) = slots[0], slots[-1]
-            if p0.data_ptr() == base + o0 and p1.data_ptr() == base + o1:
-                return
-        if all(p.data_ptr() == base + o for p, o in slots):
-            return
-        pairs = self.ordered_params() + [("deviation_network.variance", self.deviation_network.variance)]
-        with torch.no_grad():
-            for k, p in pairs:
-                off, shape = self._layout[k]
-                if p.data_ptr() != base + 4 * off:
-                    if p.dtype != torch.float32:
-                        raise TypeError(f"parameter {k} was converted to {p.dtype}; endosurf_amd computes in fp32 only")
-                    self._flat[off:off + p.numel()].copy_(p.data.reshape(-1).to(self._flat.device))
-        self._rebind()
-
-    # ---- reference query surface (endosurf.py:570-689), evaluated by the fused HIP kernels -------------------------------------
-    # Differentiable w.r.t. the network PARAMETERS (hand-written backward) when grad mode is on, and w.r.t. the query points / inputs where the
-    # reference's are: the sdf query (its derivative IS g_o), the two gradient queries (second order: es_point_vjp) and forward() (position,
-    # view direction and time: _NetForwardFn).
-    def _r(self):
-        r = self._renderer() if getattr(self, "_renderer", None) is not None else None
-        if r is None:
-            raise RuntimeError("this EndoSurfNet is not attached to an EndoSurfRenderer")
-        return r
-
-    @staticmethod
-    def _xt(x, t):
-        x = x.detach().to(torch.float32).reshape(-1, 3).contiguous()
-        t = torch.as_tensor(t, device=x.device).detach().to(torch.float32).reshape(-1)
-        if t.numel() not in (1, x.shape[0]):
-            raise ValueError("t must hold one time per point (or a single shared time)")
-        return x, (t.expand(x.shape[0]) if t.numel() == 1 else t).contiguous()
-
-    @staticmethod
-    def _wrt_points(x):
-        """``x`` if autograd should track the query points (a tensor that requires grad, with grad mode on), else None."""
-        return x if (torch.is_tensor(x) and x.requires_grad and torch.is_grad_enabled()) else None
-
-    def get_sdf_from_observed_space(self, x, t):
-        """sdf(x + deform(x, t)) [M,1]  (endosurf.py:570-579).
-
-        If ``x`` requires grad (the reference's own pattern around this call is ``autograd.grad(sdf, x, create_graph=True)``,
-        endosurf.py:585-600) the result is differentiable w.r.t. the points: d sdf / d x is the kernels' g_o = J^T g_c, attached as
-        ``sdf + <x - x.detach(), g_o>`` (value unchanged).  g_o itself carries the hand-written backward to the parameters AND (round 5)
-        to the points -- the Hessian-vector product of the query (Engine.point_input_adjoint) -- so a loss on
-        ``autograd.grad(sdf, x, create_graph=True)`` back-propagates to both, like the reference's."""
-        r = self._r()
-        with torch.cuda.device(r.device):
-            x_in = self._wrt_points(x)
-            x, t = self._xt(x, t)
-            weff, _ = r._weights()
-            if x_in is not None or (weff.requires_grad and torch.is_grad_enabled()):
-                sdf, g_o = r._point_eval(x, t, x_in=x_in)
-                if x_in is not None:
-                    xr = x_in.to(torch.float32).reshape(-1, 3)
-                    sdf = sdf + ((xr - xr.detach()) * g_o).sum(-1, keepdim=True)
-                return sdf
-            return r.sdf_observed(x, t)
-
-    def get_sdf_grad_from_observed_space(self, x, t):
-        """d sdf / d x at observed points [M,3] = J^T g_c  (endosurf.py:581-601).  Differentiable w.r.t. the parameters and -- like the
-        reference's create_graph=True result -- w.r.t. the points (``autograd.grad(g.sum(), x)`` = the Hessian of the query times the
-        incoming adjoint: one more reverse sweep of the deformation network on the SDF backward's x_c adjoint, plus the deformation
-        network's own curvature term)."""
-        r = self._r()
-        with torch.cuda.device(r.device):
-            x_in = self._wrt_points(x)
-            x, t = self._xt(x, t)
-            return r._point_eval(x, t, x_in=x_in)[1]
-
-    def get_sdf_grad_from_canonical_space(self, x):
-        """d sdf / d x_c at canonical points [M,3]  (endosurf.py:603-619): the SDF network alone.  Differentiable w.r.t. the parameters and
-        the points (the SDF network's Hessian-vector product comes out of its backward as the adjoint of x_c)."""
-        r = self._r()
-        with torch.cuda.device(r.device):
-            x_in = self._wrt_points(x)
-            x, t = self._xt(x, torch.zeros(1, device=x.device))
-            return r._point_eval(x, t, canonical=True, x_in=x_in)[1]
-
-    def get_deform_grad_from_observed_space(self, x, t):
-        """Jacobian d x_c / d x [M,3,3] (dim_out, dim_in)  (endosurf.py:621-658): three forward-mode tangents (J e_j), no grad."""
-        r = self._r()
-        with torch.cuda.device(r.device):
-            x, t = self._xt(x, t)
-            M = x.shape[0]
-            if not self.use_deform:
-                return torch.eye(3, device=x.device).expand(M, 3, 3).clone()
-            weff, packed = r._weights()
-            cols = []
-            with torch.no_grad():
-                for j in range(3):
-                    e = torch.zeros(M, 3, device=x.device)
-                    e[:, j] = 1.0
-                    pctx = r.engine.point_forward(r.engine.points(x=x, t=t, dirs=e), weff.detach(), packed, _lib.PF_DEFORM)
-                    cols.append(pctx.view("v").clone())
-            return torch.stack(cols, dim=-1)
-
-    def forward(self, inputs):
-        """cat([sdf, rgb]) [M,4] for inputs [x, d, t] [M,7]  (endosurf.py:660-689).  Differentiable w.r.t. the parameters and -- when
-        ``inputs`` requires grad -- w.r.t. the inputs (position, view direction and time: ``_NetForwardFn``)."""
-        r = self._r()
-        with torch.cuda.device(r.device):
-            weff, packed = r._weights()
-            if self._wrt_points(inputs) is not None:
-                flags = (_lib.PF_DEFORM if self.use_deform else 0) | _lib.PF_COLOR | _lib.PF_SAVE
-                sdf, rgb = _NetForwardFn.apply(weff, packed, r.engine, inputs, flags)
-                return torch.cat([sdf, rgb], -1).reshape(*inputs.shape[:-1], 4)
-            inp = inputs.detach().to(torch.float32).reshape(-1, 7)
-            x, t = self._xt(inp[:, :3], inp[:, 6])
-            d = inp[:, 3:6].contiguous()
-            pts = r.engine.points(x=x, t=t, dirs=d)
-            sdf, _, rgb = _PointEvalFn.apply(weff, packed, r.engine, pts, r._flags(weff) | _lib.PF_COLOR)
-            return torch.cat([sdf, rgb], -1)
-
-
-# ---------------------------------------------------------------------------------------------------------------
-# autograd glue
-# ---------------------------------------------------------------------------------------------------------------
-class _PackFn(torch.autograd.Function):
-    """(bias, weight_g, weight_v)* -> effective-weight buffer (+ packed MFMA fragments as a side product).
-
-    ctx never references the Function's own outputs (directly or through the model's cache): such a cycle runs through
-    C++ autograd nodes and is not collectable, which would leak the buffers every step."""
-
-    @staticmethod
-    def forward(ctx, model_ref, eng: Engine, *plist):
-        model = model_ref()
-        weff, packed = eng.weightnorm_pack(model._flat, model.use_deform)
-        ctx.model_ref, ctx.eng, ctx.flat, ctx.use_deform = model_ref, eng, model._flat, model.use_deform
-        ctx.slots = [(model._layout[key][0], p.numel(), tuple(p.shape)) for key, p in model.ordered_params()]
-        ctx.mark_non_differentiable(packed)
-        ctx.set_materialize_grads(False)      # (otherwise autograd zero-fills a 17 MB adjoint for ``packed`` at every backward)
-        return weff, packed
-
-    @staticmethod
-    def backward(ctx, dweff, _dpacked):
-        model = ctx.model_ref()
-        if model is not None:
-            model._pack_cache = None
-        if dweff is None:
-            return (None, None, *[None for _ in ctx.slots])
-        pipe = getattr(ctx.eng, "_grad_pipeline", None)
-        if pipe is not None and pipe.get("dflat") is not None and pipe.get("dweff_ptr") == dweff.data_ptr() and pipe.get("buffers") == 1:
-            pipe["adopted"] = True
-            # a pipelined data-parallel step (trainer.Trainer overlap_allreduce): the hooks behind the weight-gradient launches have
-            # already written (and are all-reducing) the finished layers' slices; the rest -- whatever the hooks left -- is done here
-            dflat = pipe["dflat"]
-            for first, n in pipe["remaining"]:
-                ctx.eng.weightnorm_backward_layers(ctx.flat, dweff, dflat, first, n)
-        else:
-            dflat = ctx.eng.weightnorm_backward(ctx.flat, dweff.contiguous(), ctx.use_deform)
-        if model is not None:
-            model._flat_grad = dflat          # the parameters' .grad are views of this buffer (used by trainer.FlatAdam)
-        return (None, None, *[dflat[off:off + n].view(shape) for off, n, shape in ctx.slots])
-
-
-class _SValFn(torch.autograd.Function):
-    """s_val = 1 / clip(exp(10 variance), 1e-6, 1e6) (endosurf.py:168, :205) in one launch; differentiable like the reference's."""
-
-    @staticmethod
-    def forward(ctx, variance, eng: Engine):
-        s = eng.variance_terms(variance.detach())
-        ctx.save_for_backward(s)
-        ctx.shape = variance.shape
-        return s.reshape(variance.shape)
-
-    @staticmethod
-    def backward(ctx, g):
-        s, = ctx.saved_tensors
-        inside = ((s > 1e-6) & (s < 1e6)).to(s.dtype)          # d/dvar exp(-10 var) = -10 s_val inside the clip range
-        return (g.reshape(1) * -10.0 * s * inside).reshape(ctx.shape), None
-
-
-class _PointEvalFn(torch.autograd.Function):
-    """Fused per-point evaluation (sdf, g_o[, rgb]) with hand-written backward to the effective weights."""
-
-    @staticmethod
-    def forward(ctx, weff, packed, eng: Engine, pts, flags: int, x_in=None):
-        """``x_in`` (optional): the caller's point tensor, so that autograd routes the adjoint of the POINTS through g_o back to it
-        (colour-less evaluations on the fp32 kernels; ``flags`` must carry PF_SAVE)."""
-        # grad mode is disabled inside Function.forward; the caller passes the save decision through ``flags``
-        pctx = eng.point_forward(pts, weff, packed, flags, fp32_only=x_in is not None)
-        ctx.pctx, ctx.eng, ctx.weff, ctx.packed = pctx, eng, weff, packed
-        ctx.pts, ctx.flags = pts, flags
-        ctx.set_materialize_grads(False)
-        ctx.wrt_x = x_in is not None
-        ctx.x_shape = tuple(x_in.shape) if x_in is not None else None
-        ctx.x_dtype = x_in.dtype if x_in is not None else None
-        outs = [pctx.view("sdf").clone(), pctx.view("go").clone()]     # own storage: outputs must not pin the workspace
-        if flags & _lib.PF_COLOR:
-            outs.append(pctx.view("rgb").clone())
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, d_sdf, d_go, d_rgb=None):
-        eng, pctx = ctx.eng, ctx.pctx
-        if not (ctx.flags & _lib.PF_SAVE):
-            raise RuntimeError("point evaluation was run without PF_SAVE; cannot backpropagate")
-        if ctx.wrt_x and d_go is None and d_rgb is None and not ctx.needs_input_grad[0]:
-            # the reference's first pass, autograd.grad(sdf, x, create_graph=True) (endosurf.py:585-600): only the adjoint of the POINTS is
-            # asked for, and through g_o alone that is identically zero (d sdf / d x = g_o is attached by the caller) -- no launch, and the
-            # workspace stays whole for the loss.backward() that follows
-            return None, None, None, None, None, torch.zeros(ctx.x_shape, device=eng.device, dtype=ctx.x_dtype)
-        if pctx is None:
-            # (the re-evaluation reads ctx.weff / ctx.packed: the buffers of THIS forward, which later parameter updates never touch)
-            # second backward through the same node (retain_graph / the reference's autograd.grad(sdf, x, create_graph=True) followed by
-            # loss.backward(): with point-differentiable outputs the first pass already went through here).  The backward kernels consume
-            # the workspace, so the forward is evaluated again -- same kernels, same inputs, same values.
-            with torch.no_grad():
-                pctx = eng.point_forward(ctx.pts, ctx.weff.detach(), ctx.packed, ctx.flags, fp32_only=ctx.wrt_x)
-        dweff = eng.point_backward(pctx, ctx.weff, ctx.packed, d_sdf, d_go, d_rgb)
-        xbar = None
-        if ctx.wrt_x and ctx.needs_input_grad[5]:
-            if d_go is None:          # through g_o alone the points' adjoint is zero (see above): no VJP launch
-                xbar = torch.zeros(ctx.x_shape, device=eng.device, dtype=ctx.x_dtype)
-            else:
-                xbar = eng.point_input_adjoint(pctx, ctx.weff, ctx.packed, d_sdf, d_go).reshape(ctx.x_shape).to(ctx.x_dtype)
-        ctx.pctx = None
-        return dweff, None, None, None, None, xbar
-
-
-class _NetForwardFn(torch.autograd.Function):
-    """EndoSurfNet.forward (reference endosurf.py:660-689) as a function of the network parameters AND of its inputs [x, d, t]:
-    (sdf [M,1], rgb [M,3]).  The backward to the effective weights is es_point_backward; the adjoint of the inputs is assembled from what
-    that backward leaves in the workspace -- xcbar, the adjoint of x_c over all paths (colour encodings, geometry features, sdf, and the
-    second-order path through the canonical normal g_c), and vbar, the adjoint of v = J d -- with two more reverse sweeps of the
-    deformation network (es_point_vjp):
-        xbar = J^T xcbar - d * curv(vbar)        (curv: the encodings' second derivative against the sweep's adjoint, ES_WS_CURV; the
-        dbar = J^T vbar                           deformation MLP is piecewise linear in its encodings, so d(J d)/dx is this diagonal
-        tbar = <xcbar, d x_c / d t>               and d(J d)/dt = 0 almost everywhere)
-    Without a deformation network x_c = x, v = d: xbar = xcbar, dbar = vbar, tbar = 0."""
-
-    @staticmethod
-    def forward(ctx, weff, packed, eng: Engine, inputs, flags: int):
-        inp = inputs.detach().to(torch.float32).reshape(-1, 7)
-        x, d, t = inp[:, :3].contiguous(), inp[:, 3:6].contiguous(), inp[:, 6].contiguous()
-        pts = eng.points(x=x, t=t, dirs=d)
-        pctx = eng.point_forward(pts, weff, packed, flags, fp32_only=True)
-        ctx.pctx, ctx.eng, ctx.weff, ctx.packed, ctx.pts, ctx.flags, ctx.d = pctx, eng, weff, packed, pts, flags, d
-        ctx.in_shape, ctx.in_dtype = tuple(inputs.shape), inputs.dtype
-        ctx.set_materialize_grads(False)
-        return pctx.view("sdf").clone(), pctx.view("rgb").clone()
-
-    @staticmethod
-    def backward(ctx, d_sdf, d_rgb):
-        eng, pctx = ctx.eng, ctx.pctx
-        if not (ctx.flags & _lib.PF_SAVE):
-            raise RuntimeError("EndoSurfNet.forward was evaluated without saved activations; cannot backpropagate")
-        if pctx is None:          # a second backward through the node: the kernels consumed the workspace, evaluate again
-            with torch.no_grad():
-                pctx = eng.point_forward(ctx.pts, ctx.weff.detach(), ctx.packed, ctx.flags, fp32_only=True)
-        M = pctx.M
-        dweff = eng.point_backward(pctx, ctx.weff, ctx.packed, d_sdf, None, d_rgb)
-        gin = None
-        if ctx.needs_input_grad[3]:
-            gin = eng.empty(M, 7)
-            xcbar, vbar = pctx.view("xcbar").clone(), pctx.view("vbar").clone()
-            if ctx.flags & _lib.PF_DEFORM:
-                def sweep(c):          # J^T c, the curvature sums and the time adjoint of one reverse sweep of the deformation network
-                    pctx.view("gc").copy_(c)
-                    _lib.check(eng.lib.es_point_vjp(_lib.C.byref(pctx.pts), _lib.ptr(ctx.packed), _lib.ptr(ctx.weff.detach()), _lib.ptr(pctx.ws),
-                                                    pctx.flags, eng.st()), "es_point_vjp")
-                    return pctx.view("go").clone(), pctx.view("curv").clone(), pctx.view("tbar").clone()
-                jx, _, tb = sweep(xcbar)
-                jv, cv, _ = sweep(vbar)
-                gin[:, :3] = jx - ctx.d * cv
-                gin[:, 3:6] = jv
-                gin[:, 6:7] = tb
-            else:
-                gin[:, :3], gin[:, 3:6] = xcbar, vbar
-                gin[:, 6] = 0.0
-            gin = gin.reshape(ctx.in_shape).to(ctx.in_dtype)
-        ctx.pctx = None
-        return dweff, None, None, gin, None
-
-
-class _Tail:
-    """Room behind a grad-enabled render's samples for the colour-less points of the calls that FOLLOW it in the reference trainer's step
-    (``renderer(rays)`` -> ``errorondepth`` -> ``surface_neighbour_error``, trainer_endosurf.py:130, :140, :155).  The render lays its point
-    workspace out for P + cap rows and evaluates the first P; each later grad-enabled point evaluation writes its points into the next free
-    rows of (aux_x, aux_t), evaluates exactly those rows (es_point_forward_rows) and deposits its adjoints in (g_sdf, g_go) when autograd
-    reaches it; the render's backward -- which autograd runs after them, see ``_TailEvalFn`` -- then back-propagates the whole workspace in
-    ONE chain of launches with the tail's stages mixed into the main ones, exactly as the fused training step does.  The three separate
-    backward chains this replaces cost 2.1 ms of a 19.6 ms step (two of them run 16 - 32 workgroups at a tile's full latency per launch).
-
-    ``cap`` is learnt: the rows the previous step asked for (EndoSurfRenderer._aux_demand); rows nobody claimed are evaluated (at whatever
-    finite points the buffer holds, with zero adjoints) before the backward, so every row of the workspace is defined."""
-
-    def __init__(self, eng: Engine, P_: int, cap: int):
-        self.P, self.cap, self.used = int(P_), int(cap), 0
-        buf = eng.zeros(8 * cap)                      # one allocation, one fill: points (x | t) and adjoints (g_sdf | g_go)
-        self.aux_x, self.aux_t = buf[:3 * cap].view(cap, 3), buf[3 * cap:4 * cap]
-        self.g_sdf, self.g_go = buf[4 * cap:5 * cap].view(cap, 1), buf[5 * cap:].view(cap, 3)
-        self.gbuf = buf[4 * cap:]                     # both adjoint buffers: cleared again behind every backward that consumed them
-        self.pctx, self.weff, self.flags = None, None, 0
-        self.pending = None                           # a deferred errorondepth evaluation placed in these rows (_PendingEod)
-
-    def room(self, m64: int, weff, flags: int) -> bool:
-        return self.pctx is not None and self.weff is weff and self.flags == flags and self.used + m64 <= self.cap
-
-
-class _TailEvalFn(torch.autograd.Function):
-    """(sdf [m,1], g_o [m,3]) of ``m`` colour-less points evaluated into rows [off, off + m) of a live render's tail (``_Tail``).
-
-    The only differentiable input is the render's ``token`` output: it makes the render node a dependency of this one, so autograd runs
-    this backward -- which merely deposits the adjoints -- BEFORE the render's (even when nothing else of the render is used in the
-    loss), and the render's backward carries them to the weights."""
-
-    @staticmethod
-    def forward(ctx, token, tail: _Tail, eng: Engine, off: int, m: int):
-        pctx = tail.pctx
-        r0 = tail.P + off
-        sdf, go = eng.empty(m, 1), eng.empty(m, 3)          # own storage: outputs must not alias the workspace
-        _lib.check(eng.lib.es_copy2(_lib.ptr(sdf), _lib.ptr(pctx.view("sdf")[r0:]), m, _lib.ptr(go), _lib.ptr(pctx.view("go")[r0:]), 3 * m,
-                                    eng.st()), "es_copy2")
-        ctx.tail, ctx.eng, ctx.off, ctx.m = tail, eng, off, m
-        ctx.set_materialize_grads(False)
-        return sdf, go
-
-    @staticmethod
-    def backward(ctx, d_sdf, d_go):
-        tail, eng, off, m = ctx.tail, ctx.eng, ctx.off, ctx.m
-        f = lambda g: None if g is None else g.detach().to(torch.float32).contiguous()
-        d_sdf, d_go = f(d_sdf), f(d_go)
-        if d_sdf is not None or d_go is not None:
-            _lib.check(eng.lib.es_copy2(_lib.ptr(tail.g_sdf[off:]), _lib.ptr(d_sdf), m if d_sdf is not None else 0,
-                                        _lib.ptr(tail.g_go[off:]), _lib.ptr(d_go), 3 * m if d_go is not None else 0, eng.st()), "es_copy2")
-        return None, None, None, None, None
-
-
-class _Lazy(torch.Tensor):
-    """A result whose producing launches have not been ISSUED yet: every torch function that touches it first issues them (on the calling
-    thread, in program order: whatever reads the value is enqueued behind them), then runs on the plain tensor.  Attribute getters
-    (``.shape``, ``.dtype``, ``.requires_grad``, ``.grad_fn`` ...) do not trigger.  Used by ``errorondepth``: see ``_PendingEod``."""
-
-    # what may be asked of the tensor without its value (everything else -- including the ``.data`` / ``.T`` getters, which hand out
-    # aliases of the storage -- issues the launches first)
-    _META = frozenset(("shape", "dtype", "device", "requires_grad", "grad_fn", "is_cuda", "is_leaf", "ndim", "layout", "names", "is_sparse",
-                       "is_quantized", "is_meta", "output_nr", "_version", "grad", "is_cpu", "itemsize", "nbytes"))
-    _META_FN = frozenset(("dim", "size", "numel", "ndimension", "nelement", "is_contiguous", "is_floating_point", "is_complex", "stride",
-                          "element_size", "get_device"))
-
-    @staticmethod
-    def wrap(t: torch.Tensor, pending):
-        r = t.as_subclass(_Lazy)
-        r._es_pending = pending
-        return r
-
-    @classmethod
-    def __torch_function__(cls, func, types, args=(), kwargs=None):
-        kwargs = kwargs or {}
-        name = getattr(func, "__name__", "")
-        meta = (name == "__get__" and getattr(getattr(func, "__self__", None), "__name__", "") in cls._META) or name in cls._META_FN
-
-        def plain(a):
-            if isinstance(a, _Lazy):
-                p = a.__dict__.get("_es_pending")
-                if p is not None and not meta:
-                    p.force()
-                return a.as_subclass(torch.Tensor)
-            if isinstance(a, (list, tuple)):
-                return type(a)(plain(b) for b in a)
-            return a
-
-        with torch._C.DisableTorchFunctionSubclass():
-            return func(*[plain(a) for a in args], **{k: plain(v) for k, v in kwargs.items()})
-
-
-class _PendingEod:
-    """``errorondepth``'s network evaluation + reductions, not issued yet.  The reference trainer reads ``sdf_loss`` / ``angle_loss`` only
-    after it has called ``surface_neighbour_error`` (trainer_endosurf.py:139-162), whose own colour-less points take the rows right
-    behind these in the render workspace's tail: the two evaluations then go out as ONE launch chain (deformation on 16-point tiles, SDF +
-    VJP on 32-row tiles: 96 workgroups at one tile's latency instead of 32, then 64, at one tile's latency EACH: 0.37 ms per step).
-    ``force()`` issues whatever is still missing; it is called by the next evaluation into the same tail (which folds these rows into
-    its launch first), by the first torch function that touches a result (``_Lazy``), by this node's backward and by the render's
-    backward -- whichever comes first; so nothing depends on the caller's order of calls, only the saving does."""
-
-    def __init__(self, renderer, tail, off, n, rays, mask, weff, packed):
-        eng = renderer.engine
-        # (weak references: the tail is kept alive by the render's autograd node, which every reader of the results reaches through this
-        # evaluation's own node; a strong one would close a cycle with ``tail.pending`` around the 6.7 GB workspace)
-        self.renderer, self._tail, self.off, self.n, self.m64 = weakref.ref(renderer), weakref.ref(tail), int(off), int(n), (int(n) + 63) // 64 * 64
-        self.rays, self.mask, self.weff, self.packed, self.eng = rays, mask, weff, packed, eng
-        self.out, self.inside = eng.empty(3), eng.empty(n, 1)
-        self.sdf, self.go = eng.empty(n, 1), eng.empty(n, 3)
-        self.rows_done, self.done = False, False
-        self.stream = torch.cuda.current_stream(eng.device)
-
-    @property
-    def tail(self):
-        t = self._tail()
-        if t is None:
-            raise RuntimeError("errorondepth's deferred evaluation outlived the render it was placed in")
-        return t
-
-    def force(self):
-        if self.done:
-            return
-        eng, tail = self.eng, self.tail
-        self.done = True
-        if tail.pending is self:
-            tail.pending = None
-        cur = torch.cuda.current_stream(eng.device)
-        with torch.no_grad(), torch.cuda.stream(self.stream):          # (on the stream the call was made on, whoever triggers it)
-            if tail.pctx is None:
-                raise RuntimeError("errorondepth's deferred evaluation outlived the render workspace it was placed in")
-            if not self.rows_done:
-                eng.point_forward_rows(tail.pctx, self.weff, self.packed, tail.P + self.off, self.m64)
-                self.rows_done = True
-            r0, n = tail.P + self.off, self.n
-            _lib.check(eng.lib.es_copy2(_lib.ptr(self.sdf), _lib.ptr(tail.pctx.view("sdf")[r0:]), n, _lib.ptr(self.go),
-                                        _lib.ptr(tail.pctx.view("go")[r0:]), 3 * n, eng.st()), "es_copy2")
-            _lib.check(eng.lib.es_eod_loss(_lib.ptr(self.rays), _lib.ptr(tail.aux_x[self.off:]), _lib.ptr(self.mask), _lib.ptr(self.sdf),
-                                           _lib.ptr(self.go), n, _lib.ptr(self.out), _lib.ptr(self.inside), eng.st()), "es_eod_loss")
-        if cur != self.stream:
-            cur.wait_stream(self.stream)
-
-
-class _LazyEodFn(torch.autograd.Function):
-    """(sdf_error, angle_error) of a ``_PendingEod``: the autograd node exists from the call on, its values from ``force()`` on.  Like
-    ``_TailEvalFn`` it hangs on the render's token and deposits the points' adjoints in the tail for the render's backward."""
-
-    @staticmethod
-    def forward(ctx, token, pending: _PendingEod):
-        ctx.pending = pending
-        ctx.set_materialize_grads(False)
-        return pending.out[0], pending.out[1]
-
-    @staticmethod
-    def backward(ctx, g_sdf_err, g_ang_err):
-        p = ctx.pending
-        if g_sdf_err is None and g_ang_err is None:
-            return None, None
-        p.force()
-        eng, tail, n = p.eng, p.tail, p.n
-        f = lambda g: None if g is None else g.detach().to(torch.float32).reshape(1)
-        ga, gb = f(g_sdf_err), f(g_ang_err)
-        _lib.check(eng.lib.es_eod_loss_backward(_lib.ptr(p.rays), _lib.ptr(p.inside), _lib.ptr(p.sdf), _lib.ptr(p.go), _lib.ptr(p.out), _lib.ptr(ga),
-                                                _lib.ptr(gb), n, _lib.ptr(tail.g_sdf[p.off:]), _lib.ptr(tail.g_go[p.off:]), eng.st()),
-                   "es_eod_loss_backward")
-        return None, None
-
-
-class _EodLossFn(torch.autograd.Function):
-    """errorondepth's reductions (reference endosurf.py:302-317) as one launch, backward one launch (es_eod_loss / es_eod_loss_backward)."""
-
-    @staticmethod
-    def forward(ctx, sdf, g_o, eng: Engine, rays, pts, mask):
-        N = rays.shape[0]
-        f = lambda a: a.detach().to(torch.float32).contiguous()
-        sdf_, go_, rays_, pts_, mask_ = f(sdf), f(g_o), f(rays), f(pts), f(mask)
-        if not (sdf_.numel() == N and go_.numel() == 3 * N and pts_.numel() == 3 * N and mask_.numel() == N):
-            raise ValueError("errorondepth expects one point, one sdf, one gradient and one mask value per ray")
-        out, inside = eng.empty(3), eng.empty(N, 1)
-        _lib.check(eng.lib.es_eod_loss(_lib.ptr(rays_), _lib.ptr(pts_), _lib.ptr(mask_), _lib.ptr(sdf_), _lib.ptr(go_), N, _lib.ptr(out),
-                                       _lib.ptr(inside), eng.st()), "es_eod_loss")
-        ctx.eng, ctx.saved, ctx.n = eng, (rays_, inside, sdf_, go_, out), N
-        ctx.shapes = (tuple(sdf.shape), tuple(g_o.shape))
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(inside)
-        return out[0], out[1], inside
-
-    @staticmethod
-    def backward(ctx, g_sdf_err, g_ang_err, _g_inside):
-        if g_sdf_err is None and g_ang_err is None:
-            return None, None, None, None, None, None
-        eng, N = ctx.eng, ctx.n
-        rays_, inside, sdf_, go_, out = ctx.saved
-        f = lambda g: None if g is None else g.detach().to(torch.float32).reshape(1)
-        ga, gb = f(g_sdf_err), f(g_ang_err)
-        d_sdf, d_go = eng.empty(N, 1), eng.empty(N, 3)
-        _lib.check(eng.lib.es_eod_loss_backward(_lib.ptr(rays_), _lib.ptr(inside), _lib.ptr(sdf_), _lib.ptr(go_), _lib.ptr(out), _lib.ptr(ga),
-                                                _lib.ptr(gb), N, _lib.ptr(d_sdf), _lib.ptr(d_go), eng.st()), "es_eod_loss_backward")
-        return d_sdf.view(ctx.shapes[0]), d_go.view(ctx.shapes[1]), None, None, None, None
-
-
-class _SnLossFn(torch.autograd.Function):
-    """surface_neighbour_error's reduction (reference endosurf.py:334-339) as one launch, backward one launch."""
-
-    @staticmethod
-    def forward(ctx, g, eng: Engine, valid):
-        N = valid.numel()
-        g_ = g.detach().to(torch.float32).contiguous()
-        if g_.numel() != 6 * N:
-            raise ValueError("surface_neighbour_error expects the gradients of N surface points followed by their N neighbours")
-        v8 = (valid.view(torch.uint8) if valid.dtype == torch.bool else valid.to(torch.uint8)).contiguous()
-        out = eng.empty(2)
-        _lib.check(eng.lib.es_sn_loss(_lib.ptr(g_), _lib.ptr(v8), N, _lib.ptr(out), eng.st()), "es_sn_loss")
-        ctx.eng, ctx.saved, ctx.n, ctx.shape = eng, (g_, v8, out), N, tuple(g.shape)
-        ctx.set_materialize_grads(False)
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g_loss):
-        if g_loss is None:
-            return None, None, None
-        eng, N = ctx.eng, ctx.n
-        g_, v8, out = ctx.saved
-        gl = g_loss.detach().to(torch.float32).reshape(1)
-        d_g = eng.empty(2 * N, 3)
-        _lib.check(eng.lib.es_sn_loss_backward(_lib.ptr(g_), _lib.ptr(v8), _lib.ptr(out), _lib.ptr(gl), N, _lib.ptr(d_g), eng.st()),
-                   "es_sn_loss_backward")
-        return d_g.view(ctx.shape), None, None
-
-
-class _RenderFn(torch.autograd.Function):
-    """render_core (reference endosurf.py:134-213) on fixed sample depths: fused point evaluation + compositing.
-    Optionally evaluates ``aux_x/aux_t`` (colour-less points: errorondepth / surface-neighbour points of a training step)
-    in the SAME kernel launches and returns their (sdf, g_o).  ctx keeps inputs and the workspace only, never outputs.
-
-    ``chunk_rays`` < N with saving enabled: the rays are processed in chunks WITHOUT keeping activations and every chunk is
-    re-evaluated (with saving) in the backward, its weight gradients accumulated: bounded memory for any batch size at the price
-    of one extra forward (the reference bounds memory with run_fn_split's net_chunk, utils.py:114-126, but autograd still keeps
-    every chunk's graph alive; here the bound is real)."""
-
-    @staticmethod
-    def forward(ctx, weff, packed, variance, eng: Engine, rays, z, sample_dist: float, cos_anneal: float, flags: int, aux_x, aux_t,
-                chunk_rays: int, tail=None):
-        """``tail`` (a fresh ``_Tail``; only without ``aux_x`` / chunking): lay the workspace out with ``tail.cap`` extra colour-less rows for
-        the point evaluations of later calls; the last output (``token``) ties their autograd nodes to this one."""
-        N, S = z.shape
-        P_ = N * S
-        ctx.tail = None
-        ctx.set_materialize_grads(False)          # unused outputs (weights, cdf, ...) arrive as None, not as zero-filled tensors
-        var1 = variance.detach().reshape(1)
-        ctx.eng, ctx.weff, ctx.packed, ctx.variance = eng, weff, packed, variance
-        ctx.geom = (rays, z, float(sample_dist), cos_anneal if torch.is_tensor(cos_anneal) else float(cos_anneal))
-        ctx.flags = flags
-        if (flags & _lib.PF_SAVE) and 0 < chunk_rays < N:
-            ctx.chunk_rays, ctx.pctx, ctx.n_aux = int(chunk_rays), None, 0
-            outs = {k: [] for k in ("color", "depth", "weights", "weight_max", "cdf", "wmax_idx", "go")}
-            eik_acc = eng.zeros(2)
-            for i in range(0, N, chunk_rays):
-                r_, z_ = rays[i:i + chunk_rays], z[i:i + chunk_rays]
-                n_ = r_.shape[0]
-                mid = eng.mid_z(z_, sample_dist)
-                # the SAME launches as the re-evaluation in the backward (saving into a workspace that is dropped right away: one chunk's
-                # worth, what the backward will allocate anyway): the loss adjoints are then taken at exactly the outputs the backward
-                # differentiates, whichever kernel family the engine selects for a saving evaluation
-                pctx = eng.point_forward(eng.points(rays=r_, z=mid, n_per_ray=S, ldz=S), weff, packed, flags | _lib.PF_COLOR)
-                a = eng.composite_args(r_, z_, pctx.view("sdf").view(-1), pctx.view("go"), pctx.view("rgb"), var1, sample_dist, cos_anneal)
-                out = eng.composite_forward(a, eik_acc=eik_acc)
-                for k in ("color", "depth", "weights", "weight_max", "cdf", "wmax_idx"):
-                    outs[k].append(out[k])
-                outs["go"].append(pctx.view("go")[:n_ * S].view(n_, S, 3).clone())
-            cat = {k: torch.cat(v, 0) for k, v in outs.items()}
-            ctx.eik_den = (eik_acc[1] + 1e-6).reshape(1)
-            eik = eik_acc[0] / ctx.eik_den[0]
-            den_out = ctx.eik_den.clone()
-            ctx.mark_non_differentiable(cat["wmax_idx"], den_out)
-            return (cat["color"], cat["depth"], cat["go"], eik, cat["weights"], cat["weight_max"], cat["cdf"], cat["wmax_idx"],
-                    eng.zeros(0, 1), eng.zeros(0, 3), den_out, eng.empty(1))
-        ctx.chunk_rays = 0
-        mid = eng.mid_z(z, sample_dist)
-        fused = aux_x is not None and aux_x.shape[0] > 0 and P_ % 64 == 0
-        if tail is not None and not fused and (flags & _lib.PF_SAVE) and P_ % 64 == 0 and P_ > 0:
-            # the colour part of a workspace laid out for P + cap rows; the tail's rows are evaluated by the calls that claim them
-            pts = eng.points(rays=rays, z=mid, n_per_ray=S, ldz=S, x=tail.aux_x, t=tail.aux_t)
-            pctx = PointCtx(eng, pts, flags | _lib.PF_COLOR, m_color=P_)
-            eng.point_forward_rows(pctx, weff, packed, 0, P_)
-            tail.pctx, tail.weff, tail.flags = pctx, weff, flags
-            ctx.tail = tail
-        else:
-            pts = eng.points(rays=rays, z=mid, n_per_ray=S, ldz=S, x=aux_x if fused else None, t=aux_t if fused else None)
-            pctx = eng.point_forward(pts, weff, packed, flags | _lib.PF_COLOR, m_color=P_ if fused else 0)
-        sdf_all, go_all = pctx.view("sdf"), pctx.view("go")
-        a = eng.composite_args(rays, z, sdf_all.view(-1), go_all, pctx.view("rgb"), var1, sample_dist, cos_anneal)
-        # own storage for every output (the 6.7 GB workspace must not outlive the backward): the compositing launch writes the samples'
-        # g_o rows a second time, es_render_finish forms gradient_o_error and its normaliser from the two batch sums and copies the
-        # auxiliary rows -- one launch where there were three clones, an add and a divide
-        out = eng.composite_forward(a, go_copy=True)
-        n_aux = aux_x.shape[0] if fused else 0
-        eik, den2 = eng.empty(1), eng.empty(2)
-        aux_sdf, aux_go = eng.empty(n_aux, 1), eng.empty(n_aux, 3)
-        _lib.check(eng.lib.es_render_finish(_lib.ptr(out["eik_acc"]), _lib.ptr(sdf_all[P_:]) if n_aux else None, _lib.ptr(go_all[P_:]) if n_aux else None,
-                                            n_aux, _lib.ptr(eik), _lib.ptr(den2), _lib.ptr(aux_sdf) if n_aux else None,
-                                            _lib.ptr(aux_go) if n_aux else None, eng.st()), "es_render_finish")
-        eik_den, den_out = den2[0:1], den2[1:2]      # the eikonal term's normaliser: kept for the backward / handed out (exact data-parallel mode)
-        ctx.pctx, ctx.eik_den = pctx, eik_den
-        ctx.n_aux = n_aux
-        ctx.mark_non_differentiable(out["wmax_idx"], den_out)
-        return (out["color"], out["depth"], out["go"], eik.reshape(()), out["weights"], out["weight_max"], out["cdf"], out["wmax_idx"], aux_sdf,
-                aux_go, den_out, eng.empty(1))
-
-    @staticmethod
-    def backward(ctx, g_color, g_depth, g_go, g_eik, g_weights, g_wmax, g_cdf, _, g_aux_sdf, g_aux_go, _g_den=None, _g_token=None):
-        eng = ctx.eng
-        tail = ctx.tail
-        if tail is not None:
-            if tail.pending is not None:          # (a deferred errorondepth nobody has read: its rows must be defined before the backward)
-                tail.pending.force()
-            # the later calls' points behind the samples: their nodes have run (they depend on this one through the token) and left
-            # their adjoints in the tail's buffers; rows nobody claimed are evaluated now, with zero adjoints
-            if tail.pctx is not None and tail.used < tail.cap:
-                eng.point_forward_rows(tail.pctx, ctx.weff, ctx.packed, tail.P + tail.used, tail.cap - tail.used)
-                tail.used = tail.cap
-            ctx.n_aux, g_aux_sdf, g_aux_go = tail.cap, tail.g_sdf, tail.g_go
-            if ctx.pctx is None:          # a second backward through this node: re-evaluate everything (main rows + the whole tail)
-                rays_, zs_, sd_, _ = ctx.geom
-                mid = eng.mid_z(zs_, sd_)
-                pts = eng.points(rays=rays_, z=mid, n_per_ray=zs_.shape[1], ldz=zs_.shape[1], x=tail.aux_x, t=tail.aux_t)
-                ctx.pctx = eng.point_forward(pts, ctx.weff, ctx.packed, ctx.flags | _lib.PF_COLOR, m_color=zs_.numel(), fp32_only=True)
-        if not (ctx.flags & _lib.PF_SAVE):
-            raise RuntimeError("render was run without saved activations; cannot backpropagate")
-        rays, zs, sample_dist, cos_anneal = ctx.geom
-        N, S = zs.shape
-        var = ctx.variance.detach()
-        var1 = var.reshape(1)
-        z = lambda g, *shape: (g.contiguous() if g is not None else eng.zeros(*shape))
-        opt = lambda g: g.contiguous() if g is not None else None
-        g_color, g_depth, g_eik = z(g_color, N, 3), z(g_depth, N, 1).view(-1), z(g_eik, 1).reshape(1)
-        g_weights, g_cdf, g_go = opt(g_weights), opt(g_cdf), opt(g_go)
-        g_wmax = g_wmax.contiguous().view(-1) if g_wmax is not None else None
-        sl = lambda g, i, j: g[i:j] if g is not None else None
-        d_invs_acc = eng.zeros(1)
-        dweff = eng.zeros(eng.n_weff) if N == 0 else None       # an empty batch has a zero gradient, not a missing one
-        C = max(1, ctx.chunk_rays if ctx.chunk_rays else N)
-        for i in range(0, N, C):
-            j = min(i + C, N)
-            if ctx.chunk_rays:          # re-evaluate this chunk with saving
-                r_, z_ = rays[i:j], zs[i:j]
-                mid = eng.mid_z(z_, sample_dist)
-                pctx = eng.point_forward(eng.points(rays=r_, z=mid, n_per_ray=S, ldz=S), ctx.weff, ctx.packed, ctx.flags | _lib.PF_COLOR)
-            else:
-                r_, z_, pctx = rays, zs, ctx.pctx
-            a = eng.composite_args(r_, z_, pctx.view("sdf").view(-1), pctx.view("go"), pctx.view("rgb"), var1, sample_dist, cos_anneal)
-            # (the auxiliary points' adjoint rows are appended by the compositing launch itself: no concatenation)
-            bw = eng.composite_backward(a, g_color[i:j], g_depth[i:j], g_eik, ctx.eik_den, g_weights=sl(g_weights, i, j), g_cdf=sl(g_cdf, i, j),
-                                        g_wmax=sl(g_wmax, i, j), g_gradients_o=sl(g_go, i, j), d_invs_acc=d_invs_acc, n_aux=ctx.n_aux,
-                                        g_aux_sdf=opt(g_aux_sdf), g_aux_go=opt(g_aux_go))
-            d_sdf, d_go = bw["d_sdf"].view(-1, 1), bw["d_go"]
-            dweff = eng.point_backward(pctx, ctx.weff, ctx.packed, d_sdf, d_go, bw["d_rgb"], dweff=dweff, staged=not ctx.chunk_rays)
-            del pctx
-        # inv_s = clip(exp(10 var), 1e-6, 1e6)  (endosurf.py:168, :852): d var = d inv_s * 10 exp(10 var) inside the clip range
-        dvar = eng.variance_terms(var, d_invs_acc=d_invs_acc).reshape(ctx.variance.shape)
-        ctx.pctx = None                                           # release the workspace as soon as it has been consumed
-        if tail is not None:
-            tail.pctx = None
-            # (a later pass through this graph -- retain_graph -- must not find this pass's adjoints where a node deposits none)
-            _lib.check(eng.lib.es_zero(_lib.ptr(tail.gbuf), 4 * tail.gbuf.numel(), eng.st()), "es_zero")
-        return dweff, None, dvar, None, None, None, None, None, None, None, None, None, None
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -1045,7 +132,7 @@ class EndoSurfRenderer(nn.Module):
 
     @staticmethod
     def _rays32(rays):
-        return rays.detach().to(torch.float32).contiguous()
+        return f32(rays)
 
     def _chunk_rays(self, N, S, flags):
         """Rays per chunk of a grad-enabled render such that its activation workspace stays within ``workspace_gb`` (0: no chunking)."""
@@ -1171,7 +258,7 @@ class EndoSurfRenderer(nn.Module):
         u = None
         if perturb:
             u = u_perturb if u_perturb is not None else torch.rand([rays.shape[0], 1], device=self.device)
-            u = u.detach().to(torch.float32).reshape(-1).contiguous()
+            u = f32(u).reshape(-1)
         upsample = iter_step >= self.important_begin_iter and self.n_importance > 0
         with torch.no_grad():
             return self.engine.sample_z(rays, u, weff.detach(), packed, self.use_deform, self.n_samples, self.n_importance,
@@ -1180,7 +267,7 @@ class EndoSurfRenderer(nn.Module):
     def _rays_from(self, rays_o, rays_d, time=None):
         n = rays_o.shape[0]
         t = time.reshape(n, 1) if time is not None else torch.zeros(n, 1, device=self.device)
-        return torch.cat([rays_o, rays_d, torch.zeros(n, 2, device=self.device), t], -1).detach().to(torch.float32).contiguous()
+        return f32(torch.cat([rays_o, rays_d, torch.zeros(n, 2, device=self.device), t], -1))
 
     @_on_device
     def up_sample(self, rays_o, rays_d, z_vals, sdf, n_importance, inv_s):
@@ -1189,12 +276,11 @@ class EndoSurfRenderer(nn.Module):
         N, n = z_vals.shape
         eng = self.engine
         rays = self._rays_from(rays_o, rays_d)
-        z = z_vals.detach().to(torch.float32).contiguous()
-        sd = sdf.detach().to(torch.float32).reshape(N, n).contiguous()
+        z = f32(z_vals)
+        sd = f32(sdf).reshape(N, n)
         S = n + int(n_importance)
         z_new, z_out, src = eng.empty(N, int(n_importance)), eng.empty(N, S), eng.empty(N, S, dtype=torch.int32)
-        _lib.check(eng.lib.es_upsample_step(_lib.ptr(rays), _lib.ptr(z), n, _lib.ptr(sd), n, N, n, int(n_importance), float(inv_s),
-                                            _lib.ptr(z_new), _lib.ptr(z_out), S, _lib.ptr(src), eng.st()), "es_upsample_step")
+        eng.upsample_step(rays, z, n, sd, n, N, n, int(n_importance), inv_s, z_new, z_out, S, src)
         return z_new
 
     @_on_device
@@ -1205,7 +291,7 @@ class EndoSurfRenderer(nn.Module):
         N, n = z_vals.shape
         m = new_z_vals.shape[1]
         eng = self.engine
-        z_new = new_z_vals.detach().to(torch.float32).contiguous()
+        z_new = f32(new_z_vals)
         z_cat = torch.cat([z_vals.detach().to(torch.float32), z_new], dim=-1)
         z_sorted, index = torch.sort(z_cat, dim=-1, stable=True)
         if last:
@@ -1214,10 +300,10 @@ class EndoSurfRenderer(nn.Module):
         weff, packed = self._weights()
         with torch.no_grad():
             sdf_new = eng.query_sdf(eng.points(rays=rays, z=z_new, n_per_ray=m, ldz=m), weff.detach(), packed, self.use_deform)
-        sd = sdf.detach().to(torch.float32).reshape(N, n).contiguous()
+        sd = f32(sdf).reshape(N, n)
         src = index.to(torch.int32).contiguous()
         out = eng.empty(N, n + m)
-        _lib.check(eng.lib.es_merge_sdf(_lib.ptr(sd), n, _lib.ptr(sdf_new), m, _lib.ptr(src), n + m, N, n, _lib.ptr(out), eng.st()), "es_merge_sdf")
+        eng.merge_sdf(sd, n, sdf_new, m, src, n + m, N, n, out)
         return z_sorted, out
 
     @_on_device
@@ -1237,9 +323,9 @@ class EndoSurfRenderer(nn.Module):
         x, t = eng.empty(M, 3), eng.empty(M)
         with torch.no_grad():
             for _ in range(int(n_secant_steps)):
-                _lib.check(eng.lib.es_secant_points(_lib.ptr(rays32), _lib.ptr(d_pred), M, _lib.ptr(x), _lib.ptr(t), eng.st()), "es_secant_points")
+                eng.secant_points(rays32, d_pred, M, x, t)
                 f_mid = eng.query_sdf(eng.points(x=x, t=t), weff.detach(), packed, self.use_deform)
-                _lib.check(eng.lib.es_secant_update(_lib.ptr(f_mid), M, float(tau), _lib.ptr(state), _lib.ptr(d_pred), eng.st()), "es_secant_update")
+                eng.secant_update(f_mid, M, tau, state, d_pred)
             for k, dst in enumerate((d_low, f_low, d_high, f_high)):
                 dst.copy_(state[:, k].reshape(dst.shape).to(dst.dtype))
         return d_pred
@@ -1279,11 +365,11 @@ class EndoSurfRenderer(nn.Module):
             _rays = torch.cat([rays_o, rays_d, torch.zeros(n, 2, device=self.device), time.reshape(n, 1)], -1).to(torch.float32).contiguous()
         weff, packed = self._weights()
         var = self.model.deviation_network.variance
-        z = z_vals.detach().to(torch.float32).contiguous()
+        z = f32(z_vals)
         aux_x = aux_t = None
         if _aux is not None:
-            aux_x = _aux[0].detach().to(torch.float32).contiguous()
-            aux_t = _aux[1].detach().to(torch.float32).reshape(-1).contiguous()
+            aux_x = f32(_aux[0])
+            aux_t = f32(_aux[1]).reshape(-1)
         flags = self._flags(weff)
         chunk = self._chunk_rays(z.shape[0], z.shape[1], flags)
         tail = self._new_tail(z.numel(), flags, chunk, z.shape[0]) if _aux is None else None
@@ -1309,15 +395,18 @@ class EndoSurfRenderer(nn.Module):
         if (flags & _lib.PF_SAVE) and not canonical and x_in is None and dirs is None:
             # a grad-enabled colour-less evaluation: into the tail of the live render if there is room (see _Tail), and counted either way
             xx, tt = x.detach().to(torch.float32).reshape(-1, 3), t.detach().to(torch.float32).reshape(-1)
-            slot = self._tail_slot(xx.shape[0], weff, flags)
-            if slot is not None and tt.numel() == xx.shape[0]:
-                eng, m = self.engine, xx.shape[0]
-                if xx.data_ptr() != slot[2].data_ptr():          # (errorondepth / surface_neighbour_error write their points in place)
-                    _lib.check(eng.lib.es_copy2(_lib.ptr(slot[2]), _lib.ptr(xx.contiguous()), 3 * m, _lib.ptr(slot[3]), _lib.ptr(tt.contiguous()), m,
-                                                eng.st()), "es_copy2")
-                return self._tail_eval(slot, m, weff, packed)
-        pts = self.engine.points(x=x.detach().to(torch.float32).contiguous(), t=t.detach().to(torch.float32).reshape(-1).contiguous(),
-                                 dirs=dirs)
+            m = xx.shape[0]
+            self._aux_demand = getattr(self, "_aux_demand", 0) + _Tail.rows64(m)          # (what the next render sizes its tail by)
+            slot = self._tail_peek(m, weff, flags)
+            if slot is not None and tt.numel() == m:
+                eng = self.engine
+                tail, token = self._live_tail
+                if xx.data_ptr() != slot.x.data_ptr():          # (errorondepth / surface_neighbour_error write their points in place)
+                    eng.copy2(slot.x, xx.contiguous(), 3 * m, slot.t, tt.contiguous(), m)
+                off = tail.claim(m)
+                tail.evaluate(eng, off, m, weff, packed)
+                return _TailEvalFn.apply(token, tail, eng, off, m)
+        pts = self.engine.points(x=f32(x), t=f32(t).reshape(-1), dirs=dirs)
         if canonical:
             flags &= ~_lib.PF_DEFORM
         if x_in is not None:
@@ -1336,7 +425,7 @@ class EndoSurfRenderer(nn.Module):
             return None
         if self.__dict__.get("_fwd_graphs"):
             self.release_forward_graphs()
-        first_guess = (n_rays + 63) // 64 * 64 + (2 * n_rays + 63) // 64 * 64
+        first_guess = _Tail.rows64(n_rays) + _Tail.rows64(2 * n_rays)
         demand, self._aux_demand = self.__dict__.get("_aux_demand", first_guess), 0
         eng = self.engine
         if demand <= 0 or chunk or P_ <= 0 or P_ % 64 or eng.split_precision or torch.cuda.is_current_stream_capturing():
@@ -1350,44 +439,21 @@ class EndoSurfRenderer(nn.Module):
         self.tails_made = getattr(self, "tails_made", 0) + 1          # (observability: how many renders hosted later calls' points)
         return _Tail(eng, P_, cap)
 
-    def _tail_slot(self, m: int, weff, flags: int, count: bool = True):
-        """(tail, row offset, x view [m,3], t view [m]) in the live render's tail for ``m`` more colour-less points, or None.
-        ``count``: add the request to the demand the next render sizes its tail by."""
-        m64 = (m + 63) // 64 * 64
-        if count:
-            self._aux_demand = getattr(self, "_aux_demand", 0) + m64
+    def _tail_peek(self, m: int, weff, flags: int):
+        """The slot (tail._Slot) of the live render's tail for ``m`` more colour-less points, or None."""
         live = getattr(self, "_live_tail", None)
         if live is None or m == 0 or not torch.is_grad_enabled():
             return None
-        tail = live[0]
-        if not tail.room(m64, weff, flags):
-            return None
-        off = tail.used
-        return tail, off, tail.aux_x[off:off + m], tail.aux_t[off:off + m]
-
-    def _tail_eval(self, slot, m: int, weff, packed):
-        tail, off = slot[0], slot[1]
-        m64 = (m + 63) // 64 * 64
-        tail.used = off + m64
-        pend = tail.pending
-        if pend is not None and not pend.done and not pend.rows_done and pend.off + pend.m64 == off and pend.stream == torch.cuda.current_stream(self.device):
-            # errorondepth's deferred rows sit right in front of these: ONE launch chain evaluates both pieces
-            self.engine.point_forward_rows(tail.pctx, weff, packed, tail.P + pend.off, pend.m64 + m64)
-            pend.rows_done = True
-            pend.force()
-        else:
-            if pend is not None:
-                pend.force()
-            self.engine.point_forward_rows(tail.pctx, weff, packed, tail.P + off, m64)
-        return _TailEvalFn.apply(self._live_tail[1], tail, self.engine, off, m)
+        return live[0].peek(m, weff, flags)
 
     def _aux_buffers(self, m: int):
-        """Where a call's ``m`` colour-less points are written: straight into the live render's tail when it has room, else fresh buffers."""
+        """Where a call's ``m`` colour-less points are written: straight into the live render's tail when it has room, else fresh buffers
+        (``_point_eval`` recognises the tail's views and counts the demand)."""
         weff, _ = self._weights()
         flags = self._flags(weff)
-        slot = self._tail_slot(m, weff, flags, count=False) if (flags & _lib.PF_SAVE) else None      # (_point_eval does the counting)
+        slot = self._tail_peek(m, weff, flags) if (flags & _lib.PF_SAVE) else None
         if slot is not None:
-            return slot[2], slot[3]
+            return slot.x, slot.t
         return self.engine.empty(m, 3), self.engine.empty(m)
 
     @_on_device
@@ -1406,20 +472,18 @@ class EndoSurfRenderer(nn.Module):
         slot = None
         if (bool(self.render_cfg.get("defer_errorondepth", True)) and (flags & _lib.PF_SAVE) and N > 0 and torch.is_grad_enabled()
                 and not torch.cuda.is_current_stream_capturing()):
-            slot = self._tail_slot(N, weff, flags, count=False)          # (counted below / by _point_eval: once)
+            slot = self._tail_peek(N, weff, flags)
         if slot is None:
             pts, time, inside = self._eod_points(rays, d_gt, mask)
             sdf, gradient_o = self._point_eval(pts, time)
             return self._eod_loss(rays, pts, mask, sdf, gradient_o)
-        tail, off = slot[0], slot[1]
-        self._aux_demand = getattr(self, "_aux_demand", 0) + (N + 63) // 64 * 64
-        if tail.pending is not None:
-            tail.pending.force()
-        inside = self._eod_points(rays, d_gt, mask, into=(slot[2], slot[3]))[2]
-        tail.used = off + (N + 63) // 64 * 64
-        pend = _PendingEod(self, tail, off, N, rays, mask.detach().to(torch.float32).reshape(-1).contiguous(), weff, packed)
-        tail.pending = pend
-        a, b = _LazyEodFn.apply(self._live_tail[1], pend)
+        tail, token = self._live_tail
+        self._aux_demand = getattr(self, "_aux_demand", 0) + _Tail.rows64(N)
+        tail.force_pending()
+        inside = self._eod_points(rays, d_gt, mask, into=(slot.x, slot.t))[2]
+        pend = _PendingEod(self.engine, tail, tail.claim(N), N, rays, f32(mask).reshape(-1), weff, packed)
+        tail.defer(pend)
+        a, b = _LazyEodFn.apply(token, pend)
         return _Lazy.wrap(a, pend), _Lazy.wrap(b, pend), inside
 
     def _eod_points(self, rays, d_gt, mask=None, into=None):
@@ -1427,17 +491,16 @@ class EndoSurfRenderer(nn.Module):
         (:306-309), one launch (es_eod_points).  ``into``: (x, t) buffers to write the points to (rows of a render's tail)."""
         N = rays.shape[0]
         x, t = into if into is not None else self._aux_buffers(N)
-        d = d_gt.detach().to(torch.float32).reshape(-1).contiguous()
+        d = f32(d_gt).reshape(-1)
         if d.numel() != N:
             raise ValueError("errorondepth expects one ground-truth depth per ray")
         inside = m = None
         if mask is not None:
-            m = mask.detach().to(torch.float32).reshape(-1).contiguous()
+            m = f32(mask).reshape(-1)
             if m.numel() != N:
                 raise ValueError("errorondepth expects one mask value per ray")
             inside = self.engine.empty(N, 1)
-        _lib.check(self.engine.lib.es_eod_points(_lib.ptr(rays), _lib.ptr(d), _lib.ptr(m), N, _lib.ptr(x), _lib.ptr(t), _lib.ptr(inside),
-                                                 self.engine.st()), "es_eod_points")
+        self.engine.eod_points(rays, d, m, N, x, t, inside)
         return (x, t, inside) if mask is not None else (x, t)
 
     def _eod_loss(self, rays, pts, mask, sdf, gradient_o):
@@ -1475,35 +538,30 @@ class EndoSurfRenderer(nn.Module):
         (endosurf.py:321-332) in one launch (es_sn_points) behind the marching's."""
         N = rays.shape[0]
         eng = self.engine
-        f = lambda a: a.detach().to(torch.float32).contiguous()
         x, t = self._aux_buffers(2 * N)
         with torch.no_grad():
             if d_i is None:
                 d_i = self.ray_marching(rays)
             if u_neigh is not None:
-                u = f(u_neigh)
+                u = f32(u_neigh)
             elif torch.cuda.is_current_stream_capturing():      # (a captured graph needs torch's graph-safe generator)
                 u = torch.rand(N, 3, device=self.device)
             else:
                 u = eng.uniform(3 * N).view(N, 3)
-            m = f(mask).reshape(-1)
+            m = f32(mask).reshape(-1)
             if m.numel() != N:
                 raise ValueError("surface_neighbour_error expects one mask value per ray")
             valid = eng.empty(N, dtype=torch.bool)
-            _lib.check(eng.lib.es_sn_points(_lib.ptr(rays), _lib.ptr(m), _lib.ptr(f(d_i).reshape(-1)), _lib.ptr(u), float(neighbour_rad), N, _lib.ptr(x),
-                                            _lib.ptr(t), _lib.ptr(valid), eng.st()), "es_sn_points")
+            eng.sn_points(rays, m, f32(d_i).reshape(-1), u, neighbour_rad, N, x, t, valid)
             return x, t, valid
 
     def _train_aux_points(self, rays, depth_gt, mask, d_i, neighbour_rad, u_neigh=None):
         """(x [3N,3], t [3N], valid [N] bool): the points of _eod_points and _sn_points (same arithmetic) in one launch."""
         N = rays.shape[0]
-        f = lambda a: a.detach().to(torch.float32).contiguous()
-        u = f(u_neigh) if u_neigh is not None else torch.rand(N, 3, device=self.device)
+        u = f32(u_neigh) if u_neigh is not None else torch.rand(N, 3, device=self.device)
         x, t = self.engine.empty(3 * N, 3), self.engine.empty(3 * N)
         valid = self.engine.empty(N, dtype=torch.bool)
-        _lib.check(self.engine.lib.es_train_aux_points(_lib.ptr(rays), _lib.ptr(f(depth_gt)), _lib.ptr(f(mask)), _lib.ptr(f(d_i)), _lib.ptr(u),
-                                                       float(neighbour_rad), N, _lib.ptr(x), _lib.ptr(t), _lib.ptr(valid), self.engine.st()),
-                   "es_train_aux_points")
+        self.engine.train_aux_points(rays, f32(depth_gt), f32(mask), f32(d_i), u, neighbour_rad, N, x, t, valid)
         return x, t, valid
 
     def _sn_loss(self, g, valid):
@@ -1649,7 +707,7 @@ class EndoSurfRenderer(nn.Module):
     def sdf_observed(self, pts, t):
         """get_sdf_from_observed_space (endosurf.py:570-579) for [M,3] points and [M] / scalar time, no grad."""
         weff, packed = self._weights()
-        x = pts.detach().to(torch.float32).contiguous()
-        tt = t.detach().to(torch.float32).reshape(-1).contiguous()
+        x = f32(pts)
+        tt = f32(t).reshape(-1)
         with torch.no_grad():
             return self.engine.query_sdf(self.engine.points(x=x, t=tt), weff.detach(), packed, self.use_deform).view(-1, 1)

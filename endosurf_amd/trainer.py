@@ -9,6 +9,9 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
+from . import _lib
+from .engine import f32, u8
+
 LOSS_WEIGHTS = dict(color=1.0, depth=1.0, sdf=1.0, angle=0.1, eikonal=0.1, surf_neig=0.1)   # base_pull.yml:23-29
 
 
@@ -110,11 +113,8 @@ class _LossFn(torch.autograd.Function):
     @staticmethod
     def sums(eng, rays, eod_pts, mask, cmask, valid_sn, out):
         """This rank's normalisers {sum cmask, sum inside, sum valid x mask, n_valid} -> out[0:4] (first launch of the exact mode)."""
-        import ctypes as C
-        from . import _lib
         N = rays.shape[0]
-        f = lambda t: t.detach().to(torch.float32).contiguous()
-        keep = [f(rays), f(eod_pts), f(mask), f(cmask), (valid_sn.view(torch.uint8) if valid_sn.dtype == torch.bool else valid_sn.to(torch.uint8)).contiguous()]
+        keep = [f32(rays), f32(eod_pts), f32(mask), f32(cmask), u8(valid_sn)]
         z3, z1 = eng.zeros(3 * N, 3), eng.zeros(3 * N, 1)
         a = _lib.es_loss_args()
         for name, t in zip(("rays", "eod_pts", "mask", "cmask", "valid_sn"), keep):
@@ -124,18 +124,15 @@ class _LossFn(torch.autograd.Function):
             setattr(a, name, _lib.ptr(t))
         a.N = N
         a.den_out = _lib.ptr(out)
-        _lib.check(eng.lib.es_train_loss(C.byref(a), eng.st()), "es_train_loss")
+        eng.train_loss(a)
 
     @staticmethod
     def forward(ctx, color_map, depth_map, eik, aux_sdf, aux_go, eng, rays, eod_pts, color_gt, depth_gt, mask, cmask, valid_sn, w, exact=None):
-        import ctypes as C
-        from . import _lib
         N = rays.shape[0]
         if mask.numel() != N or cmask.numel() != N or valid_sn.numel() != N or aux_sdf.numel() != 3 * N:
             raise ValueError("es_train_loss expects per-ray masks [N,1] and 3N auxiliary points")
-        f = lambda t: t.detach().to(torch.float32).contiguous()
-        ins = [f(color_map), f(depth_map), f(eik).reshape(1), f(aux_sdf), f(aux_go), f(rays), f(eod_pts), f(color_gt), f(depth_gt), f(mask),
-               f(cmask), (valid_sn.view(torch.uint8) if valid_sn.dtype == torch.bool else valid_sn.to(torch.uint8)).contiguous()]
+        ins = [f32(color_map), f32(depth_map), f32(eik).reshape(1), f32(aux_sdf), f32(aux_go), f32(rays), f32(eod_pts), f32(color_gt), f32(depth_gt),
+               f32(mask), f32(cmask), u8(valid_sn)]
         terms, total = eng.empty(8), eng.empty(1)
         # the five adjoints in ONE buffer (a non-unit seed of the backward pass scales them with one launch)
         gbuf = eng.empty(16 * N + 1)
@@ -152,7 +149,7 @@ class _LossFn(torch.autograd.Function):
         if exact is not None:            # (global normalisers [4+], world): see compute_loss_fused
             a.den_global, a.world = _lib.ptr(exact[0]), float(exact[1])
         a.total_out = _lib.ptr(total)
-        _lib.check(eng.lib.es_train_loss(C.byref(a), eng.st()), "es_train_loss")
+        eng.train_loss(a)
         ctx.set_materialize_grads(False)
         ctx.grads, ctx.gbuf, ctx.eng, ctx.n = grads, gbuf, eng, N
         ctx.eik_shape = eik.shape
@@ -167,10 +164,9 @@ class _LossFn(torch.autograd.Function):
         if g_total.data_ptr() == eng.ones1.data_ptr():       # the step's own seed (Trainer: loss.backward(gradient=engine.ones1)): d total = 1
             gc, gd, ge, gs, gg = ctx.grads
         else:
-            from . import _lib
             out = eng.empty(16 * N + 1)
             gt = g_total.detach().to(torch.float32).reshape(1)
-            _lib.check(eng.lib.es_scale(_lib.ptr(out), _lib.ptr(ctx.gbuf), 16 * N + 1, _lib.ptr(gt), eng.st()), "es_scale")
+            eng.scale(out, ctx.gbuf, 16 * N + 1, gt)
             gc, gd, ge, gs, gg = (out[0:3 * N].view(N, 3), out[3 * N:4 * N].view(N, 1), out[4 * N:4 * N + 1], out[4 * N + 1:7 * N + 1].view(3 * N, 1),
                                   out[7 * N + 1:16 * N + 1].view(3 * N, 3))
         return (gc, gd, ge.reshape(ctx.eik_shape), gs, gg, None, None, None, None, None, None, None, None, None, None)
@@ -178,7 +174,6 @@ class _LossFn(torch.autograd.Function):
 
 def _lib_flags_save(renderer) -> int:
     """The point-evaluation flags of a grad-enabled render of this renderer (what its workspace budget is computed for)."""
-    from . import _lib
     return (_lib.PF_DEFORM if renderer.use_deform else 0) | _lib.PF_SAVE
 
 
@@ -278,7 +273,6 @@ class FlatAdam:
         return g
 
     def step(self, grad: torch.Tensor = None, grad_scale: float = 1.0, variance_in_grad: bool = False):
-        from . import _lib
         g = self.flat_grad() if grad is None else grad
         gv = None if (variance_in_grad or self._var.grad is None) else self._var.grad
         frozen = [(p, p.detach().clone()) for p in self._all if not p.requires_grad]      # the launch updates the whole buffer
@@ -286,19 +280,12 @@ class FlatAdam:
         pg = self.param_groups[0]
         b1, b2 = pg["betas"]
         if self.scalars_dev is not None:      # captured step: (step_size, bc2_sqrt, grad_scale) live in device memory (Trainer.train_step_graph)
-            _lib.check(self.eng.lib.es_adam_step_dev(_lib.ptr(self.flat), _lib.ptr(g), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
-                                                     self.flat.numel(), b1, b2, pg["eps"], _lib.ptr(self.scalars_dev),
-                                                     _lib.ptr(gv) if gv is not None else None, self._var_off, self.eng.st()), "es_adam_step_dev")
-            if frozen:
-                with torch.no_grad():
-                    torch._foreach_copy_([p for p, _ in frozen], [v for _, v in frozen])
-            self.model._epoch += 1
-            return
-        step_size = pg["lr"] / (1.0 - b1 ** self.step_count)
-        bc2_sqrt = math.sqrt(1.0 - b2 ** self.step_count)
-        _lib.check(self.eng.lib.es_adam_step(_lib.ptr(self.flat), _lib.ptr(g), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
-                                             self.flat.numel(), b1, b2, pg["eps"], step_size, bc2_sqrt, float(grad_scale),
-                                             _lib.ptr(gv) if gv is not None else None, self._var_off, self.eng.st()), "es_adam_step")
+            self.eng.adam_step_dev(self.flat, g, self.exp_avg, self.exp_avg_sq, self.flat.numel(), b1, b2, pg["eps"], self.scalars_dev, gv, self._var_off)
+        else:
+            step_size = pg["lr"] / (1.0 - b1 ** self.step_count)
+            bc2_sqrt = math.sqrt(1.0 - b2 ** self.step_count)
+            self.eng.adam_step(self.flat, g, self.exp_avg, self.exp_avg_sq, self.flat.numel(), b1, b2, pg["eps"], step_size, bc2_sqrt, grad_scale, gv,
+                               self._var_off)
         if frozen:
             with torch.no_grad():
                 torch._foreach_copy_([p for p, _ in frozen], [v for _, v in frozen])
@@ -487,10 +474,8 @@ class Trainer:
         self.update_learning_rate(global_step)
 
         def schedule():
-            from . import _lib
-            _lib.check(r.engine.lib.es_train_schedule(_lib.ptr(g["state"]), float(self.lr_init), float(self.n_iter), float(self.warm_up_end),
-                                                      float(self.lr_alpha), float(pg["betas"][0]), float(pg["betas"][1]), 1.0 / world,
-                                                      float(r.anneal_end), _lib.ptr(g["scal"]), r.engine.st()), "es_train_schedule")
+            r.engine.train_schedule(g["state"], self.lr_init, self.n_iter, self.warm_up_end, self.lr_alpha, pg["betas"][0], pg["betas"][1], 1.0 / world,
+                                    r.anneal_end, g["scal"])
 
         def body():
             schedule()
@@ -577,7 +562,6 @@ class Trainer:
 
     def _pipeline_hook(self, stage, dweff):
         """Called by Engine.point_backward behind every weight-gradient launch of the step (main stream)."""
-        from . import _lib
         from .parallel import allreduce_flat
         eng = self.renderer.engine
         pipe = eng._grad_pipeline
