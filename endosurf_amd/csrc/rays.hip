@@ -202,8 +202,13 @@ __global__ __launch_bounds__(256) void k_merge_sdf(const float* __restrict__ sdf
     const int tot = n + n_imp;
     if (i >= N * tot) return;
     const int ray = i / tot, r = i - ray * tot;
+    // A ray whose depths hold a NaN (non-finite rays or SDF values) gets colliding ranks from k_upsample_step, which leaves entries of
+    // its permutation unwritten: whatever such an entry holds must not become an address.  Those samples read as NaN.
     const int s = src_idx[(size_t)ray * ld_out + r];
-    sdf_out[(size_t)ray * ld_out + r] = s < n ? sdf_in[(size_t)ray * ld_in + s] : sdf_new[(size_t)ray * n_imp + (s - n)];
+    float v = __builtin_nanf("");
+    if (s >= 0 && s < n) v = sdf_in[(size_t)ray * ld_in + s];
+    else if (s >= n && s < tot) v = sdf_new[(size_t)ray * n_imp + (s - n)];
+    sdf_out[(size_t)ray * ld_out + r] = v;
 }
 
 __global__ __launch_bounds__(256) void k_mid_z(const float* __restrict__ z, int ldz, int N, int S, float sample_dist,

@@ -272,13 +272,19 @@ class Engine:
     def sample_z(self, rays, u_perturb, weff, packed, use_deform, n_samples, n_importance, up_sample_steps, upsample: bool,
                  trace: Optional[list] = None, racing: bool = False):
         """Coarse sampling + SDF-guided hierarchical up-sampling (reference render_rays, endosurf.py:71-110).
-        Returns z [N, S] (S = n_samples (+ n_importance)).  ``racing``: this chain shares the GPU with another chain of small launches
-        (the secant iterations of a training step): its coarse query runs on 32-point tiles (es_query_sdf_tiles)."""
+        Returns z [N, S] (S = n_samples (+ up_sample_steps * (n_importance // up_sample_steps))).  ``racing``: this chain shares the GPU
+        with another chain of small launches (the secant iterations of a training step): its coarse query runs on 32-point tiles
+        (es_query_sdf_tiles)."""
         N = rays.shape[0]
         n = n_samples
         sample_dist = 2.0 / n_samples
         do_up = upsample and n_importance > 0 and up_sample_steps > 0
-        S = n + (n_importance if do_up else 0)
+        n_imp = n_importance // up_sample_steps if do_up else 0
+        if do_up and n_imp == 0:
+            raise ValueError(f"n_importance = {n_importance} gives no new sample in any of the {up_sample_steps} up-sampling steps")
+        # what the steps really add: up_sample_steps * (n_importance // up_sample_steps) columns, like the reference's loop
+        # (endosurf.py:95-110) -- fewer than n_importance when it is not a multiple of up_sample_steps
+        S = n + up_sample_steps * n_imp
         if do_up and not racing and trace is None and N > 0 and n_importance % up_sample_steps == 0 and not self._use_x3(N * n):
             # the same launches in the same order, issued by ONE library call (es_sample_z) instead of ~15: a step that ends in a host
             # sync (the reference trainer's loss.item()) starts with an empty queue, and this chain of small launches is where the GPU
@@ -294,7 +300,6 @@ class Engine:
             trace.append(zc[:, :n].clone())
         if not do_up:
             return zc
-        n_imp = n_importance // up_sample_steps
         zn = self.empty(N, S)
         # (racing: never TALLER than 32 points -- a batch the library would give 16- or 32-point tiles anyway keeps the library's choice)
         sdf_c = self.query_sdf(self.points(rays=rays, z=zc, n_per_ray=n, ldz=S), weff, packed, use_deform,

@@ -65,6 +65,11 @@ class EndoSurfRenderer(nn.Module):
         self.n_importance = render_cfg["n_importance"]
         self.important_begin_iter = render_cfg["important_begin_iter"]
         self.up_sample_steps = render_cfg["up_sample_steps"]
+        if self.n_importance > 0 and (self.up_sample_steps <= 0 or self.n_importance % self.up_sample_steps):
+            # the up-sampling loop adds up_sample_steps * (n_importance // up_sample_steps) samples, while every sample count derived from
+            # the configuration says n_samples + n_importance; the reference's render_rays raises on such a configuration as well (its
+            # s_val reshape, endosurf.py:131)
+            raise ValueError(f"n_importance ({self.n_importance}) must be a multiple of up_sample_steps ({self.up_sample_steps})")
         self.net_chunk = render_cfg["net_chunk"]
         self.use_deform = self.model.use_deform
         # Training keeps ~103 KB of activations per point for the hand-written backward (csrc/workspace.h).  A render whose

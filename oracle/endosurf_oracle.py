@@ -259,6 +259,43 @@ def d_over_z(d):
 
 
 # --------------------------------------------------------------------------------------
+# ray marching: bracket search and secant update on given profiles (endosurf.py:379-448)
+# --------------------------------------------------------------------------------------
+def march_bracket(val, d_prop):
+    """First sign change of ``val`` [N, n] (= -(sdf - tau) at the proposals ``d_prop`` [N, n]) and the secant bracket around it
+    (endosurf.py:379-406).  Returns (mask, mask_0_not_occupied, d_low, f_low, d_high, f_high), all [N]: ``mask`` = a hit (the first
+    sign change runs from negative to positive and the first proposal is not occupied); the bracket is that of the section
+    torch.min picks on every ray, meaningful where ``mask`` holds."""
+    N, n_steps = val.shape
+    mask_0_not_occupied = val[:, 0] < 0
+    sign = torch.cat([torch.sign(val[:, :-1] * val[:, 1:]), torch.ones(N, 1, dtype=val.dtype)], -1)
+    cost = sign * torch.arange(n_steps, 0, -1, dtype=val.dtype)
+    values, indices = torch.min(cost, -1)
+    ar = torch.arange(N)
+    mask_sign_change = values < 0
+    mask_neg_to_pos = val[ar, indices] < 0
+    mask = mask_sign_change & mask_neg_to_pos & mask_0_not_occupied
+    ind2 = torch.clamp(indices + 1, max=n_steps - 1)
+    return mask, mask_0_not_occupied, d_prop[ar, indices], val[ar, indices], d_prop[ar, ind2], val[ar, ind2]
+
+
+def secant_estimate(d_low, f_low, d_high, f_high):
+    """The secant method's next depth (endosurf.py:428, :448)."""
+    return -f_low * (d_high - d_low) / (f_high - f_low) + d_low
+
+
+def secant_step(d_low, f_low, d_high, f_high, d_pred, f_mid):
+    """One secant iteration (endosurf.py:438-448) for f_mid = sdf(o + d_pred d / d.z) - tau: NOT negated, unlike the bracket's values
+    (the reference's sign convention, kept as is).  Returns (d_low, f_low, d_high, f_high, d_pred)."""
+    lo = f_mid < 0
+    d_low = torch.where(lo, d_pred, d_low)
+    f_low = torch.where(lo, f_mid, f_low)
+    d_high = torch.where(lo, d_high, d_pred)
+    f_high = torch.where(lo, f_high, f_mid)
+    return d_low, f_low, d_high, f_high, secant_estimate(d_low, f_low, d_high, f_high)
+
+
+# --------------------------------------------------------------------------------------
 # renderer                                                       src/renderer/endosurf.py
 # --------------------------------------------------------------------------------------
 class OracleRenderer:
@@ -459,35 +496,19 @@ class OracleRenderer:
         t = time[:, None, :].expand(N, n_steps, 1).reshape(-1, 1)
         with torch.no_grad():
             val = -(self.net.sdf_observed(pts, t).reshape(N, n_steps) - tau)
-        mask_0_not_occupied = val[:, 0] < 0
-        sign = torch.cat([torch.sign(val[:, :-1] * val[:, 1:]), torch.ones(N, 1, dtype=val.dtype)], -1)
-        cost = sign * torch.arange(n_steps, 0, -1, dtype=val.dtype)
-        values, indices = torch.min(cost, -1)
-        ar = torch.arange(N)
-        mask_sign_change = values < 0
-        mask_neg_to_pos = val[ar, indices] < 0
-        mask = mask_sign_change & mask_neg_to_pos & mask_0_not_occupied
-        d_low = d_prop[ar, indices][mask]
-        f_low = val[ar, indices][mask]
-        ind2 = torch.clamp(indices + 1, max=n_steps - 1)
-        d_high = d_prop[ar, ind2][mask]
-        f_high = val[ar, ind2][mask]
+        mask, mask_0_not_occupied, d_low, f_low, d_high, f_high = march_bracket(val, d_prop)
+        d_low, f_low, d_high, f_high = d_low[mask], f_low[mask], d_high[mask], f_high[mask]
         out = torch.ones(N, dtype=rays.dtype)
         if int(mask.sum()) != 0:
             rm = rays[mask]
             om, dm, tm = rm[:, :3], rm[:, 3:6], rm[:, 8:9]
             dzm = dm / dm[:, 2:]                                   # no epsilon here (endosurf.py:427)
-            d_pred = -f_low * (d_high - d_low) / (f_high - f_low) + d_low
+            d_pred = secant_estimate(d_low, f_low, d_high, f_high)
             for _ in range(n_secant_steps):
                 p_mid = om + d_pred[:, None] * dzm
                 with torch.no_grad():
                     f_mid = self.net.sdf_observed(p_mid, tm)[:, 0] - tau
-                lo = f_mid < 0
-                d_low = torch.where(lo, d_pred, d_low)
-                f_low = torch.where(lo, f_mid, f_low)
-                d_high = torch.where(lo, d_high, d_pred)
-                f_high = torch.where(lo, f_high, f_mid)
-                d_pred = -f_low * (d_high - d_low) / (f_high - f_low) + d_low
+                d_low, f_low, d_high, f_high, d_pred = secant_step(d_low, f_low, d_high, f_high, d_pred, f_mid)
             out[mask] = d_pred
         out[~mask] = float("inf")
         out[~mask_0_not_occupied] = 0.0

@@ -19,11 +19,11 @@ import weightgen
 from gpu_util import renderer_for
 from oracle import endosurf_oracle as O
 from oracle_util import RENDER_CFG
+from shapes_util import SEED, inputs as _inputs
 from test_gpu_backward import FLOOR, POINT_TOL, _dump, _grad_table
 
 pytestmark = pytest.mark.gpu
 
-SEED = 41
 _RENDERERS, _ORACLE = {}, {}
 # oracle passes that two cases share (atomic + deterministic mode, the workspace-history case): kept; every other one is dropped after use
 REUSED = {("dense", True, 65, True), ("dense", True, 1024, True), ("dense", True, 1100, True), ("dense", True, 1400, True),
@@ -44,54 +44,6 @@ def _oracle_params(use_deform, dtype=torch.float64):
     state = weightgen.make_state(SEED, "trained", use_deform)
     params = {k: torch.tensor(v, dtype=dtype, requires_grad=True) for k, v in state.items()}
     return O.OracleNet(params, use_deform), params
-
-
-RELU_MARGIN = 1e-5
-
-
-def _relu_margin(net, x, d, t):
-    """Smallest |pre-activation| over the ReLU layers of the deformation and colour networks, per point (fp64, the oracle's weights).
-    The gradient is discontinuous where one of them is 0: a point within fp32 rounding of such a kink can take the other branch in
-    the kernels, which moves a whole tensor by ~1e-3 at these batch sizes and says nothing about the backward."""
-    with torch.no_grad():
-        pe = net.point_eval(x, d, t, with_color=True)
-        ins = {"color_network": torch.cat([O.freq_encode(pe["x_c"], 10), pe["g_c"], O.freq_encode(pe["d_c"], 4), pe["feat"]], -1)}
-        if net.use_deform:
-            ins["deform_network"] = torch.cat([O.freq_encode(x, 6), O.freq_encode(t, 6)], -1)
-        margin = torch.full((x.shape[0],), float("inf"), dtype=x.dtype)
-        for name, e in ins.items():
-            u = e
-            for l in range(8):
-                W, b = net._wb(name, l)
-                if l == 4:
-                    u = torch.cat([u, e], -1) / O.SQRT2
-                a = u @ W.t() + b
-                margin = torch.minimum(margin, a.abs().min(-1)[0])
-                u = torch.relu(a)
-    return margin
-
-
-def _inputs(M, seed, use_deform=True, screen=None):
-    """Points, view directions, times and upstream adjoints of (sdf, g_o, rgb): the construction of test_point_backward.  Rows
-    ``screen`` (default: all) are redrawn until they keep RELU_MARGIN from every ReLU kink."""
-    rng = np.random.default_rng(seed)
-
-    def draw(n):
-        x = rng.uniform(-0.7, 0.7, size=(n, 3)).astype(np.float32)
-        d = rng.normal(size=(n, 3)); d /= np.linalg.norm(d, axis=-1, keepdims=True)
-        return torch.from_numpy(x), torch.from_numpy(d.astype(np.float32)), torch.from_numpy(rng.uniform(size=(n,)).astype(np.float32))
-    x, d, t = draw(M)
-    rows = torch.arange(M) if screen is None else torch.as_tensor(np.asarray(screen, np.int64))
-    net = O.OracleNet({k: torch.tensor(v, dtype=torch.float64) for k, v in weightgen.make_state(SEED, "trained", use_deform).items()}, use_deform)
-    for _ in range(64):
-        near = rows[_relu_margin(net, x[rows].double(), d[rows].double(), t[rows].double()[:, None]) < RELU_MARGIN]
-        if near.numel() == 0:
-            break
-        x[near], d[near], t[near] = draw(near.numel())
-    else:
-        raise AssertionError("could not place the points away from the ReLU kinks")
-    ws, wg, wc = (torch.from_numpy(rng.normal(size=s).astype(np.float32)) for s in ((M, 1), (M, 3), (M, 3)))
-    return x, d, t, ws, wg, wc
 
 
 def _oracle_point_grads(key, use_deform, x, d, t, ws, wg, wc, n_color):

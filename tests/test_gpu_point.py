@@ -6,6 +6,7 @@ import torch
 import weightgen
 from oracle import endosurf_oracle as O
 from oracle_util import CASES, T, load_case, oracle_for
+from shapes_util import FORWARD_GATE, RELU_MARGIN, relu_margin
 
 pytestmark = pytest.mark.gpu
 
@@ -55,6 +56,17 @@ def test_point_forward(mode, use_deform, M, color):
         assert qd(ctx.view("feat"), pe["feat"]) < 5e-5
         assert qd(ctx.view("rgb"), pe["rgb"], 0.98) < 5e-5
         assert qd(ctx.view("rgb"), pe["rgb"]) < 5e-2
+    # the rows that keep RELU_MARGIN from every ReLU kink (the quantiles above make room for the others): MAXIMUM gates on every buffer,
+    # those of test_gpu_forward_shapes.py, which sweeps the shapes
+    ok = relu_margin(net, x.double(), d.double(), t.double()[:, None]) >= RELU_MARGIN
+    assert int(ok.sum()) >= M // 2
+    if bool(ok.any()):
+        names = {"xc": "x_c", "sdf": "sdf", "gc": "g_c", "go": "g_o"}
+        names.update({"feat": "feat", "rgb": "rgb"} if color else {})
+        for k, ref in names.items():
+            assert qd(ctx.view(k)[ok.cuda()], pe[ref][ok]) < FORWARD_GATE[k], k
+        if use_deform:
+            assert qd(ctx.view("v")[ok.cuda()], jd[ok]) < FORWARD_GATE["v"]
 
 
 @pytest.mark.parametrize("name", CASES)
