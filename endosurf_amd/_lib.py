@@ -115,12 +115,15 @@ PROTOTYPES = {
     "es_uniform": (_I, [_P, C.c_longlong, C.c_ulonglong, C.c_ulonglong, _P, _P]),
     "es_scale": (_I, [_P, _P, C.c_longlong, _P, _P]),
     "es_render_finish": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "es_iso_scratch_bytes": (C.c_int64, [_I, _I, _I]),
+    "es_iso_count": (_I, [_P, _I, _I, _I, C.c_double, _P, _P, _P]),
+    "es_iso_emit": (_I, [_P, _I, _I, _I, C.c_double, _P, C.c_longlong, C.c_longlong, _P, _P, _P, _P]),
     "es_timing_enable": (_I, [_I]),
     "es_timing_drain": (_I, [_I, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "es_kernel_name": (C.c_char_p, [_I]),
 }
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 QUERY_TILE_RACING = 32      # include/endosurf_hip.h ES_QUERY_TILE_RACING
 PF_DEFORM, PF_COLOR, PF_SAVE, PF_X3 = 1, 2, 4, 8
 WS_XC, WS_V, WS_SDF, WS_FEAT, WS_GC, WS_GO, WS_RGB = range(7)

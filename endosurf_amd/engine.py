@@ -599,6 +599,28 @@ class Engine:
         check(self.lib.es_adam_step_dev(ptr(flat), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), n, beta1, beta2, eps, ptr(scalars_dev), ptr(grad_var),
                                         var_off, self.st()), "es_adam_step_dev")
 
+    # ---- iso-surface extraction (csrc/iso.hip) -------------------------------------------------------
+    def iso_surface(self, field: torch.Tensor, threshold: float = 0.0):
+        """The level set ``field == threshold`` of a device field [nx, ny, nz] as a welded, oriented triangle mesh, triangulated like
+        ``meshing.marching_tetrahedra``: (verts [V,3] fp32 in index coordinates, tris [T,3] int32, edge_ends [V,2] int32 = linear grid
+        ids of each vertex's inside and outside end), all on the device.  The two counts are the only thing read back to the host."""
+        if field.dim() != 3 or field.device != self.device:
+            raise _lib.EndoSurfHipError(f"iso_surface takes a [nx, ny, nz] field on {self.device} (got {tuple(field.shape)} on {field.device})")
+        u = f32(field)
+        nx, ny, nz = (int(s) for s in u.shape)
+        nbytes = int(self.lib.es_iso_scratch_bytes(nx, ny, nz))
+        if nbytes < 0:
+            check(1, "es_iso_scratch_bytes")
+        scratch = self.empty(nbytes, dtype=torch.uint8)
+        totals = self.empty(2, dtype=torch.int64)
+        check(self.lib.es_iso_count(ptr(u), nx, ny, nz, float(threshold), ptr(scratch), ptr(totals), self.st()), "es_iso_count")
+        V, T = (int(v) for v in totals.tolist())
+        if max(V, T) >= 1 << 31:
+            raise _lib.EndoSurfHipError(f"iso_surface: {V} vertices / {T} triangles do not fit int32 indices")
+        verts, ends, tris = self.empty(V, 3), self.empty(V, 2, dtype=torch.int32), self.empty(T, 3, dtype=torch.int32)
+        check(self.lib.es_iso_emit(ptr(u), nx, ny, nz, float(threshold), ptr(scratch), V, T, ptr(verts), ptr(ends), ptr(tris), self.st()), "es_iso_emit")
+        return verts, tris, ends
+
     # ---- per-kernel timers (csrc/timing.hip) ---------------------------------------------------------
     def timing_enable(self, on: bool):
         self._timing_on = bool(on)          # (events cannot be recorded inside a captured graph: the renderer's captured forward stands down)

@@ -677,11 +677,9 @@ class EndoSurfRenderer(nn.Module):
             z = torch.zeros_like(rgb)
             return torch.where(valid, rgb, z), torch.where(valid, g, z), d_out
 
-    @_on_device
-    def extract_fields(self, bound_min, bound_max, resolution, t, net_chunk=1 << 22):
-        """SDF on a resolution^3 linspace grid at time ``t`` (reference extract_fields, utils.py:139-157, with the query of
-        extract_observation_geometry): the grid coordinates are generated on the device, sampled by the fused query kernel in
-        launches of ``net_chunk`` points and returned with ONE device-to-host copy as numpy [R,R,R] (x-major like the reference)."""
+    def _field_on_device(self, bound_min, bound_max, resolution, t, net_chunk=1 << 22):
+        """The SDF on a resolution^3 linspace grid at time ``t`` as a DEVICE tensor [R,R,R] (x-major): the grid coordinates are generated
+        on the device and sampled by the fused query kernel in launches of ``net_chunk`` points."""
         R = int(resolution)
         bmin = torch.as_tensor(bound_min, dtype=torch.float32).cpu()
         bmax = torch.as_tensor(bound_max, dtype=torch.float32).cpu()
@@ -693,13 +691,34 @@ class EndoSurfRenderer(nn.Module):
             xx, yy, zz = torch.meshgrid(ax[0][i:i + per_x], ax[1], ax[2], indexing="ij")
             pts = torch.stack([xx.reshape(-1), yy.reshape(-1), zz.reshape(-1)], -1)
             u[i * R * R:(i + per_x) * R * R] = self.sdf_observed(pts, tt).reshape(-1)
-        return u.reshape(R, R, R).cpu().numpy()
+        return u.reshape(R, R, R)
 
     @_on_device
-    def extract_observation_geometry(self, t, bound_min, bound_max, resolution, threshold=0.0, net_chunk=1 << 22, cpu=True):
+    def extract_fields(self, bound_min, bound_max, resolution, t, net_chunk=1 << 22):
+        """SDF on a resolution^3 linspace grid at time ``t`` (reference extract_fields, utils.py:139-157, with the query of
+        extract_observation_geometry): the grid coordinates are generated on the device, sampled by the fused query kernel in
+        launches of ``net_chunk`` points and returned with ONE device-to-host copy as numpy [R,R,R] (x-major like the reference)."""
+        return self._field_on_device(bound_min, bound_max, resolution, t, net_chunk).cpu().numpy()
+
+    def _mesh_on_device(self, t, bound_min, bound_max, resolution, threshold, net_chunk):
+        """(vertices [V,3] in world coordinates, triangles [T,3] int32) as device tensors: field, iso-surface and the index -> world map
+        all on the GPU (the field never leaves it; the host reads the two counts)."""
+        u = self._field_on_device(bound_min, bound_max, resolution, t, net_chunk)
+        verts, tris, _ = self.engine.iso_surface(u, threshold)
+        bmin = torch.as_tensor(bound_min, dtype=torch.float32).to(self.device).reshape(1, 3)
+        bmax = torch.as_tensor(bound_max, dtype=torch.float32).to(self.device).reshape(1, 3)
+        return verts / (resolution - 1.0) * (bmax - bmin) + bmin, tris
+
+    @_on_device
+    def extract_observation_geometry(self, t, bound_min, bound_max, resolution, threshold=0.0, net_chunk=1 << 22, cpu=True, on_device=False):
         """(vertices, triangles) of the observed-space surface at time t (reference endosurf.py:490-500 + extract_geometry,
-        utils.py:128-136).  Field sampling runs on the GPU; the iso-surface extractor is PyMCubes when installed (as in the
-        reference), otherwise endosurf_amd.meshing.marching_tetrahedra (different triangulation of the same level set)."""
+        utils.py:128-136).  Field sampling runs on the GPU.  By default the field is copied to the host and the iso-surface extractor
+        is PyMCubes when installed (as in the reference), otherwise endosurf_amd.meshing.marching_tetrahedra (different triangulation
+        of the same level set).  ``on_device=True`` extracts on the GPU as well (``Engine.iso_surface``: marching_tetrahedra's
+        triangulation, fp32 vertices, int32 triangles) and returns numpy arrays when ``cpu`` else device tensors."""
+        if on_device:
+            vertices, triangles = self._mesh_on_device(t, bound_min, bound_max, resolution, threshold, net_chunk)
+            return (vertices.cpu().numpy(), triangles.cpu().numpy()) if cpu else (vertices, triangles)
         from .meshing import iso_surface
         u = self.extract_fields(bound_min, bound_max, resolution, t, net_chunk)
         vertices, triangles = iso_surface(u, threshold)
@@ -707,6 +726,51 @@ class EndoSurfRenderer(nn.Module):
         b_min = torch.as_tensor(bound_min, dtype=torch.float32).cpu().numpy()
         vertices = vertices / (resolution - 1.0) * (b_max - b_min)[None, :] + b_min[None, :]
         return vertices, triangles
+
+    @_on_device
+    def extract_observation_mesh(self, t, bound_min, bound_max, resolution, threshold=0.0, net_chunk=1 << 22, view_point=None, refine_steps=0):
+        """The observed-space surface at time t as a coloured mesh, device tensors only (what the reference's demo assembles from
+        extract_observation_geometry + renderonpts, trainer_endosurf.py:403-460): ``vertices`` [V,3] world coordinates, ``triangles``
+        [T,3] int32, ``normals`` [V,3] the analytic observed-space SDF gradient at the vertices normalised as renderonpts does, ``sdf``
+        [V] the SDF at the vertices, and with a ``view_point`` [3] ``colors`` [V,3] = renderonpts(vertices, normalize(vertices -
+        view_point), t).  ``refine_steps`` Newton steps v -= (sdf - threshold) g / |g|^2, each clamped to half a grid cell, pull the
+        vertices onto the level set before the attributes are taken (linear interpolation leaves an O(h^2) residual).  ``net_chunk``
+        bounds the grid points per query launch; the vertices are evaluated min(net_chunk, 131072) at a time (a point evaluation keeps
+        ~10 KB of workspace per point, a query none)."""
+        vertices, triangles = self._mesh_on_device(t, bound_min, bound_max, resolution, threshold, net_chunk)
+        tt = torch.as_tensor(t, dtype=torch.float32, device=self.device).reshape(-1)[:1]
+        chunk = max(1, min(int(net_chunk), 1 << 17))
+
+        def sdf_grad(v):
+            with torch.no_grad():
+                out = [self._point_eval(v[i:i + chunk], tt) for i in range(0, v.shape[0], chunk)]
+            return torch.cat([o[0] for o in out], 0).reshape(-1, 1), torch.cat([o[1] for o in out], 0)
+
+        out = {"vertices": vertices, "triangles": triangles}
+        if vertices.shape[0] == 0:
+            out.update(normals=vertices.clone(), sdf=vertices.new_zeros(0))
+            if view_point is not None:
+                out["colors"] = vertices.clone()
+            return out
+        bmin = torch.as_tensor(bound_min, dtype=torch.float32).to(self.device).reshape(1, 3)
+        bmax = torch.as_tensor(bound_max, dtype=torch.float32).to(self.device).reshape(1, 3)
+        half_cell = 0.5 * (bmax - bmin) / (resolution - 1.0)
+        for _ in range(int(refine_steps)):
+            s, g = sdf_grad(vertices)
+            step = (s - threshold) * g / (g * g).sum(-1, keepdim=True).clamp_min(1e-20)
+            vertices = vertices - torch.maximum(torch.minimum(step, half_cell), -half_cell)
+        out["vertices"] = vertices
+        if view_point is None:
+            s, g = sdf_grad(vertices)
+            out["normals"] = g / (torch.linalg.norm(g, ord=2, dim=-1, keepdim=True) + 1e-10)
+        else:
+            vp = torch.as_tensor(view_point, dtype=torch.float32).to(self.device).reshape(1, 3)
+            dirs = vertices - vp
+            dirs = dirs / torch.linalg.norm(dirs, ord=2, dim=-1, keepdim=True)
+            out["colors"], out["normals"] = self.renderonpts(vertices, dirs, tt, net_chunk=chunk, cpu=False)
+            s, _ = sdf_grad(vertices)
+        out["sdf"] = s.reshape(-1)
+        return out
 
     @_on_device
     def sdf_observed(self, pts, t):

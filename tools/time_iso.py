@@ -1,0 +1,77 @@
+#!/usr/bin/env python3
+"""Time a mesh extraction stage by stage on the GPU box, on the trained golden case: field sampling (the SDF query over the grid),
+the on-device iso-surface (Engine.iso_surface: classify + scans, the read of the two counts, emit) and, next to it, today's host step
+(the device-to-host copy of the field + meshing.marching_tetrahedra).  Events on the launch stream, one warm-up, median of 5.
+
+    python tools/time_iso.py [--res 128 256 512] [--host-max 256] [--out FILE.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tests"))
+import torch
+
+from endosurf_amd.meshing import marching_tetrahedra
+from gpu_util import renderer_for_case
+from oracle_util import load_case
+
+
+def median_ms(fn, reps=5):
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        out.append(a.elapsed_time(b))
+    return statistics.median(out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--res", type=int, nargs="+", default=[128, 256, 512])
+    ap.add_argument("--host-max", type=int, default=256, help="largest resolution at which the host extractor is timed")
+    ap.add_argument("--out", default=None, help="also write the rows to this JSON file (one JSON line per resolution is always printed)")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs the GPU"
+    r = renderer_for_case(load_case("trained_deform"))
+    bmin, bmax, t = [-1.0, -1.0, -1.0], [1.0, 1.0, 1.0], torch.tensor([0.37])
+    rows = []
+    with torch.cuda.device(r.device):
+        for R in args.res:
+            row = {"R": R, "field_ms": median_ms(lambda: r._field_on_device(bmin, bmax, R, t))}
+            u = r._field_on_device(bmin, bmax, R, t)
+            row["iso_ms"] = median_ms(lambda: r.engine.iso_surface(u, 0.0))
+            v, f, _ = r.engine.iso_surface(u, 0.0)
+            row["V"], row["T"] = v.shape[0], f.shape[0]
+            if R <= args.host_max:
+                host = []
+                for _ in range(3):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    un = u.cpu().numpy()
+                    t1 = time.perf_counter()
+                    marching_tetrahedra(un, 0.0)
+                    host.append((time.perf_counter() - t0, t1 - t0))
+                row["host_copy_ms"] = 1e3 * statistics.median(h[1] for h in host)
+                row["host_total_ms"] = 1e3 * statistics.median(h[0] for h in host)
+            rows.append(row)
+            print(json.dumps(row))
+            del u, v, f
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fo:
+            json.dump(rows, fo, indent=1)
+
+
+if __name__ == "__main__":
+    main()
