@@ -18,6 +18,7 @@
 #include "../../include/endosurf_hip.h"
 #include "iso_table.h"
 #include "launch.h"
+#include "scan.h"
 
 namespace es {
 
@@ -121,31 +122,6 @@ __device__ __forceinline__ void chunk_load(const unsigned short* __restrict__ co
 }
 __device__ __forceinline__ int code_verts(unsigned c) { return __popc(c & 0x7fu); }
 __device__ __forceinline__ int code_tris(unsigned c) { return (int)((c >> 8) & 15u); }
-
-// inclusive scan across the 64 lanes (rays.hip wscan_add, for integers)
-template <class T>
-__device__ __forceinline__ T wscan_add(T v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const T t = __shfl_up(v, o, 64); if (lane >= o) v += t; }
-    return v;
-}
-// exclusive scan of (a, b) over the 256 threads of a workgroup; ``total`` receives the workgroup's sums
-template <class T>
-__device__ __forceinline__ void block_scan2(T& a, T& b, T (&part)[4][2], T (&total)[2]) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const T ia = wscan_add(a, lane), ib = wscan_add(b, lane);
-    if (lane == 63) { part[wv][0] = ia; part[wv][1] = ib; }
-    __syncthreads();
-    T oa = 0, ob = 0, ta = 0, tb = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        if (w < wv) { oa += part[w][0]; ob += part[w][1]; }
-        ta += part[w][0]; tb += part[w][1];
-    }
-    a = oa + ia - a; b = ob + ib - b;
-    total[0] = ta; total[1] = tb;
-    __syncthreads();
-}
 
 __global__ __launch_bounds__(256) void k_iso_blocksum(const unsigned short* __restrict__ code, long long N, int* __restrict__ bsum) {
     __shared__ int part[4][2];

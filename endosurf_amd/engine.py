@@ -621,6 +621,81 @@ class Engine:
         check(self.lib.es_iso_emit(ptr(u), nx, ny, nz, float(threshold), ptr(scratch), V, T, ptr(verts), ptr(ends), ptr(tris), self.st()), "es_iso_emit")
         return verts, tris, ends
 
+    # ---- narrow-band field (csrc/band.hip) ---------------------------------------------------------------
+    def band_field(self, sample, axes, threshold: float = 0.0, block: int = 8, lipschitz: float = 1.0, max_fraction: float = 0.5,
+                   net_chunk: int = 1 << 22):
+        """A device field [nx, ny, nz] on the lattice ``axes`` (three 1-D fp32 device tensors) whose ``iso_surface`` is the one of the
+        densely sampled field, built from ``sample(x[M,3]) -> [M]`` (any device callable) evaluated near the level set only: the scheme,
+        its exactness contract and its limit are those of ``meshing.band_field``, the numpy twin of this method (same block sets, same
+        values; the kernels are csrc/band.hip).  ``sample`` sees at most ``net_chunk`` points per call and must give a point the same
+        value whatever batch it arrives in.  The host reads two integers per round (the seeds, then each growth round).
+        Returns (field, stats, block_round [nbx, nby, nbz] int32: 0 = never evaluated, 1 = seed, r = activated by growth round r - 1);
+        ``stats``: dense_points, evaluated_points (coarse lattice and duplicated face points included), blocks, seed_blocks,
+        active_blocks, rounds, fallback."""
+        from .meshing import band_margin
+        if len(axes) != 3 or any(a.dim() != 1 or a.device != self.device for a in axes):
+            raise _lib.EndoSurfHipError(f"band_field takes three 1-D axes on {self.device}")
+        ax = [f32(a) for a in axes]
+        nx, ny, nz = (int(a.shape[0]) for a in ax)
+        B, thr, chunk = int(block), float(threshold), max(1, int(net_chunk))
+        nbytes = int(self.lib.es_band_scratch_bytes(nx, ny, nz, B))
+        if nbytes < 0:
+            check(1, "es_band_scratch_bytes")
+        nb = [-(-(n - 1) // B) for n in (nx, ny, nz)]
+        NB, N, Nc = nb[0] * nb[1] * nb[2], nx * ny * nz, (nb[0] + 1) * (nb[1] + 1) * (nb[2] + 1)
+        ends = torch.stack([torch.stack([a[0], a[-1]]) for a in ax]).tolist()          # (one small read: the world size of a block)
+        margin = band_margin(ends, (nx, ny, nz), B, lipschitz)
+        scratch = self.empty(nbytes, dtype=torch.uint8)
+        totals = self.empty(2, dtype=torch.int64)
+        axp, st = [ptr(a) for a in ax], self.st()
+
+        def lattice(stride, total, out):          # sample the (coarse) lattice in runs of ``chunk`` points
+            for p0 in range(0, total, chunk):
+                c = min(chunk, total - p0)
+                x = self.empty(c, 3)
+                check(self.lib.es_band_lattice_points(*axp, nx, ny, nz, stride, p0, c, ptr(x), st), "es_band_lattice_points")
+                out[p0:p0 + c] = sample(x).reshape(-1)
+
+        coarse = self.empty(Nc)
+        lattice(B, Nc, coarse)
+        check(self.lib.es_band_seed(ptr(coarse), nx, ny, nz, B, thr, margin, ptr(scratch), ptr(totals), st), "es_band_seed")
+        n_list, n_pts = (int(v) for v in totals.tolist())
+        stats = {"dense_points": N, "evaluated_points": Nc, "blocks": NB, "seed_blocks": n_list, "active_blocks": n_list, "rounds": 0,
+                 "fallback": False}
+        field = self.empty(N)
+        block_round = scratch[:4 * NB].view(torch.int32).view(*nb)
+        if n_list > float(max_fraction) * NB:          # the band cannot win: sample the lattice itself
+            lattice(1, N, field)
+            stats.update(evaluated_points=Nc + N, active_blocks=NB, fallback=True)
+            return field.view(nx, ny, nz), stats, block_round.clone()
+        check(self.lib.es_band_fill(nx, ny, nz, B, ptr(scratch), ptr(field), st), "es_band_fill")
+        r = 1
+        while n_list:
+            for m0 in range(0, n_pts, chunk):
+                c = min(chunk, n_pts - m0)
+                x = self.empty(c, 3)
+                check(self.lib.es_band_points(*axp, nx, ny, nz, B, ptr(scratch), n_list, m0, c, ptr(x), st), "es_band_points")
+                vals = f32(sample(x).reshape(-1))
+                check(self.lib.es_band_scatter(ptr(vals), nx, ny, nz, B, ptr(scratch), n_list, m0, c, ptr(field), st), "es_band_scatter")
+            stats["evaluated_points"] += n_pts
+            check(self.lib.es_band_grow(ptr(field), nx, ny, nz, B, thr, r, ptr(scratch), ptr(totals), st), "es_band_grow")
+            n_list, n_pts = (int(v) for v in totals.tolist())
+            stats["active_blocks"] += n_list
+            stats["rounds"] += 1 if n_list else 0
+            r += 1
+        return field.view(nx, ny, nz), stats, block_round.clone()
+
+    def iso_surface_band(self, sample, axes, threshold: float = 0.0, block: int = 8, lipschitz: float = 1.0, max_fraction: float = 0.5,
+                         net_chunk: int = 1 << 22):
+        """``iso_surface`` of the field ``sample`` takes on the lattice ``axes``, sampled near the level set only (``band_field``):
+        (verts, tris, edge_ends, stats).  The mesh holds, complete and bit-identical, every vertex-connected component of the dense
+        lattice's mesh that crosses a seed block: all of it when |grad u| <= ``lipschitz`` holds in the blocks that were culled.  With
+        a smaller ``lipschitz`` (0 = sign changes of the block corners only) a closed component smaller than a block that no block
+        corner sees can be lost."""
+        field, stats, _ = self.band_field(sample, axes, threshold, block, lipschitz, max_fraction, net_chunk)
+        verts, tris, ends = self.iso_surface(field, threshold)
+        return verts, tris, ends, stats
+
     # ---- per-kernel timers (csrc/timing.hip) ---------------------------------------------------------
     def timing_enable(self, on: bool):
         self._timing_on = bool(on)          # (events cannot be recorded inside a captured graph: the renderer's captured forward stands down)

@@ -93,3 +93,97 @@ def iso_surface(u: np.ndarray, threshold: float = 0.0):
     except ImportError:
         pass
     return marching_tetrahedra(u, threshold)
+
+
+# ---- narrow-band field (host twin of csrc/band.hip / Engine.band_field) ---------------------------------------------------------------
+def band_margin(ends, shape, block, lipschitz):
+    """``lipschitz`` times the world-space diagonal of a full block of ``block`` cells on a lattice of ``shape`` points whose axes run
+    from ends[a][0] to ends[a][1] (fp64 arithmetic: Engine.band_field and band_field pass the same number to the seed rule)."""
+    import math
+    return float(lipschitz) * math.sqrt(sum((block * (float(hi) - float(lo)) / (n - 1)) ** 2 for (lo, hi), n in zip(ends, shape)))
+
+
+def band_field(sample, axes, threshold=0.0, block=8, lipschitz=1.0, max_fraction=0.5, return_blocks=False):
+    """A field on the lattice ``axes`` (three 1-D coordinate arrays) whose marching_tetrahedra mesh is the dense field's, built from
+    evaluations of ``sample(x[M,3]) -> [M]`` near the level set only (numpy twin of ``Engine.band_field``, same block sets, same values).
+
+    Blocks of ``block`` cells per axis.  A block is a SEED when the 'inside' flags (u < threshold, NaN outside) of its 8 corners differ,
+    a corner is NaN, or no corner is farther than ``lipschitz`` * (world diagonal of a block) from the level; seeds are evaluated on all
+    their points, and a block next to an evaluated one is activated as well when a value on the shared face has the other sign than its
+    corners, until no face does.  Inactive blocks are filled with their corner value farthest from the level.  If the seeds are more
+    than ``max_fraction`` of the blocks the lattice is evaluated densely instead (``fallback``).
+
+    The mesh of the result contains, complete and with the dense mesh's coordinates, every vertex-connected component of the dense mesh
+    that crosses a seed block; it is the dense mesh when |grad u| <= lipschitz holds in the blocks that were culled.  With a smaller
+    ``lipschitz`` a closed component that fits between the block corners can be lost.
+
+    Returns (field [nx,ny,nz] float32, stats[, block_round [nbx,nby,nbz] int32: 0 = never evaluated, 1 = seed, r = activated by the
+    (r-1)-th growth round])."""
+    axes = [np.asarray(a, np.float32).reshape(-1) for a in axes]
+    shape = tuple(len(a) for a in axes)
+    B = int(block)
+    if len(axes) != 3 or min(shape) < 2:
+        raise ValueError("band_field needs three axes of at least 2 points")
+    if not 2 <= B <= 32:
+        raise ValueError("block must be in 2..32")
+    thr = float(threshold)
+    nb = tuple(-(-(n - 1) // B) for n in shape)
+    NB, N = nb[0] * nb[1] * nb[2], shape[0] * shape[1] * shape[2]
+
+    def evaluate(ix, iy, iz):
+        x = np.stack([axes[0][ix], axes[1][iy], axes[2][iz]], -1).reshape(-1, 3)
+        return np.asarray(sample(x), np.float32).reshape(-1)
+
+    cidx = [np.minimum(np.arange(b + 1) * B, n - 1) for b, n in zip(nb, shape)]
+    ci, cj, ck = np.meshgrid(*cidx, indexing="ij")
+    uc = evaluate(ci, cj, ck).reshape(ci.shape)
+    corner = np.stack([uc[dx:dx + nb[0], dy:dy + nb[1], dz:dz + nb[2]] for dx, dy, dz in _CORNER])          # [8, nbx, nby, nbz]
+    c64 = corner.astype(np.float64)
+    cin = c64 < thr
+    nan = np.isnan(c64)
+    dev = np.where(nan, -1.0, np.abs(c64 - thr))
+    far_c = np.argmax(dev, axis=0)                                          # the first corner with the largest |u - thr|
+    far = np.take_along_axis(dev, far_c[None], 0)[0] > band_margin([(a[0], a[-1]) for a in axes], shape, B, lipschitz)
+    fill = np.take_along_axis(corner, far_c[None], 0)[0]
+    seed = (cin.any(0) != cin.all(0)) | nan.any(0) | ~far
+    rnd = seed.astype(np.int32)
+    stats = {"dense_points": N, "evaluated_points": int(uc.size), "blocks": NB, "seed_blocks": int(seed.sum()), "active_blocks": int(seed.sum()),
+             "rounds": 0, "fallback": False}
+    if stats["seed_blocks"] > float(max_fraction) * NB:
+        gi, gj, gk = np.meshgrid(*[np.arange(n) for n in shape], indexing="ij")
+        field = evaluate(gi, gj, gk).reshape(shape)
+        stats.update(evaluated_points=stats["evaluated_points"] + N, active_blocks=NB, fallback=True)
+        return (field, stats, rnd) if return_blocks else (field, stats)
+    bof = [np.minimum(np.arange(n) // B, b - 1) for n, b in zip(shape, nb)]
+    field = np.ascontiguousarray(fill[np.ix_(*bof)], np.float32)
+
+    def span(b, axis):          # the closed index range of block coordinate b
+        return slice(b * B, min((b + 1) * B, shape[axis] - 1) + 1)
+
+    r = 1
+    while True:
+        new = np.argwhere(rnd == r)
+        if len(new) == 0:
+            break
+        idx = [np.meshgrid(*[np.arange(span(b[a], a).start, span(b[a], a).stop) for a in range(3)], indexing="ij") for b in new]
+        vals = evaluate(*[np.concatenate([g[a].reshape(-1) for g in idx]) for a in range(3)])
+        stats["evaluated_points"] += int(vals.size)
+        o = 0
+        for b, g in zip(new, idx):
+            field[span(b[0], 0), span(b[1], 1), span(b[2], 2)] = vals[o:o + g[0].size].reshape(g[0].shape)
+            o += g[0].size
+        for b in new:
+            for axis in range(3):
+                for side in (-1, 1):
+                    q = b.copy()
+                    q[axis] += side
+                    if not 0 <= q[axis] < nb[axis] or rnd[tuple(q)] != 0:
+                        continue
+                    sl = [span(b[a], a) for a in range(3)]
+                    plane = max(b[axis], q[axis]) * B
+                    sl[axis] = slice(plane, plane + 1)
+                    if ((field[tuple(sl)].astype(np.float64) < thr) != (float(fill[tuple(q)]) < thr)).any():
+                        rnd[tuple(q)] = r + 1
+        r += 1
+    stats.update(active_blocks=int((rnd > 0).sum()), rounds=int(rnd.max()) - 1 if rnd.max() > 0 else 0)
+    return (field, stats, rnd) if return_blocks else (field, stats)

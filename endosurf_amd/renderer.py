@@ -709,13 +709,55 @@ class EndoSurfRenderer(nn.Module):
         bmax = torch.as_tensor(bound_max, dtype=torch.float32).to(self.device).reshape(1, 3)
         return verts / (resolution - 1.0) * (bmax - bmin) + bmin, tris
 
+    def _mesh_on_device_band(self, t, bound_min, bound_max, resolution, threshold, net_chunk, band):
+        """``_mesh_on_device`` from a field sampled near the surface only, plus the counts of ``Engine.band_field``.  ``band``: True or
+        a dict of block / lipschitz / max_fraction."""
+        u, stats = self._band_field_on_device(bound_min, bound_max, resolution, t, threshold, net_chunk, {} if band is True else dict(band))
+        verts, tris, _ = self.engine.iso_surface(u, threshold)
+        bmin = torch.as_tensor(bound_min, dtype=torch.float32).to(self.device).reshape(1, 3)
+        bmax = torch.as_tensor(bound_max, dtype=torch.float32).to(self.device).reshape(1, 3)
+        return verts / (resolution - 1.0) * (bmax - bmin) + bmin, tris, stats
+
+    def _band_field_on_device(self, bound_min, bound_max, resolution, t, threshold, net_chunk, band):
+        """``_field_on_device`` with the SDF queried near the level set only (``Engine.band_field``): the same linspace axes, hence the
+        same coordinates, and always the 64-point-tile query, whose per-point result does not depend on the batch -- the kernel the
+        dense path runs for every launch above 16 384 points, so a band value is the dense value bit for bit.  (With
+        ``engine.split_precision`` on, launches of ``engine.x3_query_min`` points or more go to the split-precision query as they do in
+        ``query_sdf``; the bit-identity statement is made for the default fp32 path only.)"""
+        unknown = set(band) - {"block", "lipschitz", "max_fraction"}
+        if unknown:
+            raise TypeError(f"band takes block, lipschitz and max_fraction (got {sorted(unknown)})")
+        R = int(resolution)
+        bmin = torch.as_tensor(bound_min, dtype=torch.float32).cpu()
+        bmax = torch.as_tensor(bound_max, dtype=torch.float32).cpu()
+        ax = [torch.linspace(float(bmin[i]), float(bmax[i]), R, device=self.device) for i in range(3)]
+        tt = torch.as_tensor(t, dtype=torch.float32, device=self.device).reshape(-1)[:1]
+        weff, packed = self._weights()
+        weff = weff.detach()
+
+        def sample(x):
+            with torch.no_grad():
+                return self.engine.query_sdf(self.engine.points(x=x, t=tt), weff, packed, self.use_deform, tile_points=64)
+
+        u, stats, _ = self.engine.band_field(sample, ax, threshold, net_chunk=net_chunk, **band)
+        return u, stats
+
     @_on_device
-    def extract_observation_geometry(self, t, bound_min, bound_max, resolution, threshold=0.0, net_chunk=1 << 22, cpu=True, on_device=False):
+    def extract_observation_geometry(self, t, bound_min, bound_max, resolution, threshold=0.0, net_chunk=1 << 22, cpu=True, on_device=False,
+                                     band=None):
         """(vertices, triangles) of the observed-space surface at time t (reference endosurf.py:490-500 + extract_geometry,
         utils.py:128-136).  Field sampling runs on the GPU.  By default the field is copied to the host and the iso-surface extractor
         is PyMCubes when installed (as in the reference), otherwise endosurf_amd.meshing.marching_tetrahedra (different triangulation
         of the same level set).  ``on_device=True`` extracts on the GPU as well (``Engine.iso_surface``: marching_tetrahedra's
-        triangulation, fp32 vertices, int32 triangles) and returns numpy arrays when ``cpu`` else device tensors."""
+        triangulation, fp32 vertices, int32 triangles) and returns numpy arrays when ``cpu`` else device tensors.  With ``on_device``,
+        ``band=True`` or ``band=dict(block=8, lipschitz=1.0, max_fraction=0.5)`` queries the SDF near the surface only (see
+        ``extract_observation_mesh``); the default ``None`` samples every grid point."""
+        use_band = band is not None and band is not False
+        if use_band and not on_device:
+            raise ValueError("band needs on_device=True (the narrow-band field is assembled on the GPU)")
+        if use_band:
+            vertices, triangles, _ = self._mesh_on_device_band(t, bound_min, bound_max, resolution, threshold, net_chunk, band)
+            return (vertices.cpu().numpy(), triangles.cpu().numpy()) if cpu else (vertices, triangles)
         if on_device:
             vertices, triangles = self._mesh_on_device(t, bound_min, bound_max, resolution, threshold, net_chunk)
             return (vertices.cpu().numpy(), triangles.cpu().numpy()) if cpu else (vertices, triangles)
@@ -728,7 +770,8 @@ class EndoSurfRenderer(nn.Module):
         return vertices, triangles
 
     @_on_device
-    def extract_observation_mesh(self, t, bound_min, bound_max, resolution, threshold=0.0, net_chunk=1 << 22, view_point=None, refine_steps=0):
+    def extract_observation_mesh(self, t, bound_min, bound_max, resolution, threshold=0.0, net_chunk=1 << 22, view_point=None, refine_steps=0,
+                                 band=None):
         """The observed-space surface at time t as a coloured mesh, device tensors only (what the reference's demo assembles from
         extract_observation_geometry + renderonpts, trainer_endosurf.py:403-460): ``vertices`` [V,3] world coordinates, ``triangles``
         [T,3] int32, ``normals`` [V,3] the analytic observed-space SDF gradient at the vertices normalised as renderonpts does, ``sdf``
@@ -736,8 +779,22 @@ class EndoSurfRenderer(nn.Module):
         view_point), t).  ``refine_steps`` Newton steps v -= (sdf - threshold) g / |g|^2, each clamped to half a grid cell, pull the
         vertices onto the level set before the attributes are taken (linear interpolation leaves an O(h^2) residual).  ``net_chunk``
         bounds the grid points per query launch; the vertices are evaluated min(net_chunk, 131072) at a time (a point evaluation keeps
-        ~10 KB of workspace per point, a query none)."""
-        vertices, triangles = self._mesh_on_device(t, bound_min, bound_max, resolution, threshold, net_chunk)
+        ~10 KB of workspace per point, a query none).
+
+        ``band=True`` or ``band=dict(block=8, lipschitz=1.0, max_fraction=0.5)`` queries the SDF only in blocks of ``block`` grid cells
+        near the surface (``Engine.band_field``, csrc/band.hip) instead of at all resolution^3 points, and adds ``stats`` (a dict of
+        counts: dense_points, evaluated_points, blocks, seed_blocks, active_blocks, rounds, fallback) to the result.  A block is
+        examined when its corners change sign or none of them is farther than ``lipschitz`` * (block diagonal) from the level -- the
+        SDF is trained towards |grad| = 1 --, and blocks next to an examined one are added as long as the surface is seen to cross their
+        shared face.  Every connected piece of the dense mesh that passes through an examined block comes out complete and
+        bit-identical, in the dense vertex and triangle order: the whole mesh when |grad sdf| <= lipschitz holds in the culled blocks.
+        What a too small ``lipschitz`` can lose is a closed floater smaller than a block that no block corner sees.  Bit-identity is
+        stated for the default fp32 query; with ``engine.split_precision`` the band follows ``query_sdf``'s choice of kernel per launch.
+        The default ``None`` is the dense path."""
+        if band is not None and band is not False:
+            vertices, triangles, stats = self._mesh_on_device_band(t, bound_min, bound_max, resolution, threshold, net_chunk, band)
+        else:
+            (vertices, triangles), stats = self._mesh_on_device(t, bound_min, bound_max, resolution, threshold, net_chunk), None
         tt = torch.as_tensor(t, dtype=torch.float32, device=self.device).reshape(-1)[:1]
         chunk = max(1, min(int(net_chunk), 1 << 17))
 
@@ -747,6 +804,8 @@ class EndoSurfRenderer(nn.Module):
             return torch.cat([o[0] for o in out], 0).reshape(-1, 1), torch.cat([o[1] for o in out], 0)
 
         out = {"vertices": vertices, "triangles": triangles}
+        if stats is not None:
+            out["stats"] = stats
         if vertices.shape[0] == 0:
             out.update(normals=vertices.clone(), sdf=vertices.new_zeros(0))
             if view_point is not None:

@@ -73,10 +73,14 @@ def main():
     print(f"mesh: {len(v)} vertices, {len(f)} triangles")
     # the same surface without leaving the GPU: welded mesh, analytic normals, colours seen from a point in front of the scene
     t1 = time.perf_counter()
-    m = renderer2.extract_observation_mesh(torch.tensor([0.5]), [-1, -1, -1], [1, 1, 1], resolution=256, view_point=[0.0, 0.0, -1.5], refine_steps=1)
+    m = renderer2.extract_observation_mesh(torch.tensor([0.5]), [-1, -1, -1], [1, 1, 1], resolution=256, view_point=[0.0, 0.0, -1.5], refine_steps=1,
+                                           band=True)          # the SDF is queried near the surface only
     torch.cuda.synchronize()
     print(f"on-device mesh at 256^3: {m['vertices'].shape[0]} vertices, {m['triangles'].shape[0]} triangles, median |sdf| at the vertices "
           f"{float(m['sdf'].abs().median()) if m['sdf'].numel() else 0.0:.2e}, {time.perf_counter() - t1:.2f} s")
+    st = m["stats"]
+    print(f"narrow band: {st['evaluated_points']} of {st['dense_points']} grid points queried ({100.0 * st['evaluated_points'] / st['dense_points']:.1f} %), "
+          f"{st['active_blocks']} of {st['blocks']} blocks ({st['seed_blocks']} seeds, {st['rounds']} growth rounds), fallback {st['fallback']}")
     assert np.isfinite(psnr) and len(v) > 0 and m["vertices"].shape[0] > 0
 
 

@@ -2,8 +2,10 @@
 """Time a mesh extraction stage by stage on the GPU box, on the trained golden case: field sampling (the SDF query over the grid),
 the on-device iso-surface (Engine.iso_surface: classify + scans, the read of the two counts, emit) and, next to it, today's host step
 (the device-to-host copy of the field + meshing.marching_tetrahedra).  Events on the launch stream, one warm-up, median of 5.
+``--band`` adds the narrow-band path (Engine.band_field, csrc/band.hip): the field assembled from queries near the surface only
+(band_field_ms), field + iso-surface (band_total_ms, next to dense_total_ms), its counts, and whether the mesh is the dense one.
 
-    python tools/time_iso.py [--res 128 256 512] [--host-max 256] [--out FILE.json]
+    python tools/time_iso.py [--res 128 256 512] [--host-max 256] [--band] [--block 8] [--lipschitz 1.0] [--out FILE.json]
 """
 import argparse
 import json
@@ -40,6 +42,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--res", type=int, nargs="+", default=[128, 256, 512])
     ap.add_argument("--host-max", type=int, default=256, help="largest resolution at which the host extractor is timed")
+    ap.add_argument("--band", action="store_true", help="also time the narrow-band extraction and compare its mesh with the dense one")
+    ap.add_argument("--block", type=int, default=8)
+    ap.add_argument("--lipschitz", type=float, default=1.0)
     ap.add_argument("--out", default=None, help="also write the rows to this JSON file (one JSON line per resolution is always printed)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU"
@@ -64,6 +69,17 @@ def main():
                     host.append((time.perf_counter() - t0, t1 - t0))
                 row["host_copy_ms"] = 1e3 * statistics.median(h[1] for h in host)
                 row["host_total_ms"] = 1e3 * statistics.median(h[0] for h in host)
+            if args.band:
+                band = dict(block=args.block, lipschitz=args.lipschitz)
+                field = lambda: r._band_field_on_device(bmin, bmax, R, t, 0.0, 1 << 22, band)
+                row["band_field_ms"] = median_ms(field)
+                row["band_total_ms"] = median_ms(lambda: r.engine.iso_surface(field()[0], 0.0))
+                row["dense_total_ms"] = median_ms(lambda: r.engine.iso_surface(r._field_on_device(bmin, bmax, R, t), 0.0))
+                ub, stats = field()
+                bv, bf, _ = r.engine.iso_surface(ub, 0.0)
+                row.update(band, **stats, evaluated_fraction=stats["evaluated_points"] / stats["dense_points"],
+                           mesh_equal=bool(torch.equal(bv, v) and torch.equal(bf, f)), speedup_total=row["dense_total_ms"] / row["band_total_ms"])
+                del ub, bv, bf
             rows.append(row)
             print(json.dumps(row))
             del u, v, f
