@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: training rays/s of EndoSurf's renderer hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--full] [--config 2|3|4|5] [--dump-outputs DIR]
+
+A plain run does what the headline needs and nothing else: it sets up the workload, runs W warm-up steps, times K steps, writes
+``--dump-outputs`` and prints the line (``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``, the workload's
+description; every other section of the line is null and ``full`` is false).  ``--full`` adds, after the timed steps and outside them,
+everything else this file measures: the same step with the marching early exit, the host issue time, the per-kernel timers and the
+roofline made from them, the HBM accounting, at N > 1 the collective's timings and the replica check, the CPU baseline and the extras.
 
 N > 1: one rank per GPU over RCCL.  Either launched by ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N``
 (RANK / LOCAL_RANK / WORLD_SIZE in the environment) or directly as ``python bench.py --gpus N``, which re-executes itself under
@@ -22,15 +28,17 @@ same inputs and their dumps compare array for array.  With ``ES_DETERMINISTIC=1`
 runs of ONE build (``--steps 50 --warmup 5``) differed by 6e-7 in the loss, 8e-6 of the largest element in ``params``, 1e-4 in the colour / depth
 maps and up to 1e-2 of the largest element in the per-sample arrays (``weights``, ``gradients_o``: single samples of the hierarchical sampling move).
 
-The DEFAULT invocation (config 2, training) appends, after the headline and outside its timed region, ``cpu_baseline`` and ``extras``:
-cfg2 forward-only, cfg2 in the opt-in split-precision mode, cfg3, cfg4 and one cfg5 frame -- each ``{ms_per_step, value,
-roofline: {kernel, frac, peak, end_to_end}}`` from a few steps of a fresh renderer (``--no-extras`` / ``--headline-only`` skip them).  N > 1
-lines carry ``ranks_seen_by_collective`` (an all-reduce of ones), ``ms_per_step_min / max`` over the ranks and ``allreduce_ms`` (HIP events
-around the flat-bucket all-reduce).
+``--full`` on the default workload (config 2, training) appends, after the headline and outside its timed region, ``cpu_baseline`` and
+``extras``: the reference trainer's own call sequence, cfg2 forward-only, cfg2 in the opt-in split-precision mode, cfg3, cfg4 and
+one cfg5 frame -- each ``{ms_per_step, value, roofline: {kernel, frac, peak, end_to_end}}`` from a few steps of a fresh renderer
+(``--no-cpu-baseline`` / ``--no-extras`` / ``--headline-only`` take parts of ``--full`` away again).  N > 1 lines carry
+``ranks_seen_by_collective`` (an all-reduce of ones) and ``ms_per_step_min / max`` over the ranks, and time the step replayed from the
+whole-step hipGraph, because the rule that picks their headline reads it (``Workload.probe_graph``); with ``--full`` also ``allreduce_ms`` (HIP
+events around the flat-bucket all-reduce) and ``collective_proof``.
 
 ``value`` is the DATA-INDEPENDENT step: ray marching evaluates all 128 proposals of every ray, as the reference does.  The early
 exit at each ray's first sign change (bit-identical results, data-dependent saving) is reported next to it as
-``config.with_early_exit``.  Weak scaling: every rank draws its own ray batch, one RCCL all-reduce of the 6.6 MB gradient bucket per
+``config.with_early_exit`` (``--full``).  Weak scaling: every rank draws its own ray batch, one RCCL all-reduce of the 6.6 MB gradient bucket per
 step.  Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -527,8 +535,10 @@ class Workload:
                    rule="headline = the replayed step iff rank-max host_issue_ms > 0.8 x eager ms_per_step and the replayed step is faster")
         return out
 
-    def measure(self, warmup, steps, timing_steps=3, early_exit_extra=True):
-        """warm-up, the timed region, (train) the same step with the marching early exit, then a few instrumented steps."""
+    def measure(self, warmup, steps, timing_steps=3, early_exit_extra=True, full=True):
+        """warm-up and the timed region; ``full``: then (train) the same step with the marching early exit, the host issue time and a few
+        instrumented steps.  Without ``full`` nothing runs after the timed region except what the headline itself depends on: the
+        whole-step hipGraph probe (and the host issue time its rule reads) where ``graph_probe`` is set."""
         eng, mode = self.eng, self.mode
         march_block = eng.march_block
         if mode == "train":
@@ -540,7 +550,7 @@ class Workload:
         # the same step with ray marching's early exit (blocks of 32 proposals; tiles whose rays have all passed their first sign change
         # return at once; results bit-identical): data-dependent, reported as an extra
         extra = None
-        if mode == "train" and march_block and early_exit_extra and not self.use_graph:      # (a captured step keeps the marching mode it was captured with)
+        if full and mode == "train" and march_block and early_exit_extra and not self.use_graph:      # (a captured step keeps the marching mode it was captured with)
             eng.march_block = march_block
             self.step(nxt)
             dte, _ = self.timed(nxt + 1, steps)
@@ -549,21 +559,24 @@ class Workload:
                          note="results bit-identical to the headline step; on this synthetic init-weight scene every ray's first sign change "
                               "falls in the first block of 32 proposals (best case)")
             eng.march_block = 0
-        issue_ms = self.host_issue_ms(nxt) if mode != "frame" else None
+        want_probe = mode == "train" and self.graph_probe and not self.use_graph
+        issue_ms = self.host_issue_ms(nxt) if mode != "frame" and (full or want_probe) else None
         nxt += 5
         # N > 1 (cold-run kit): the same step replayed from the whole-step hipGraph -- a step that needs NO host work between its first
         # and its last launch.  Its time is this rank's GPU-bound step time (on one GPU it is within 1 % of the eager step), so
         # eager - graph is the time per step the GPU spent waiting for this rank's host; and when the host is the limiter (rank-max
         # host_issue_ms > 0.8 x ms_per_step) and the replayed step is faster, the replayed step IS the headline (config says so).
         probe = None
-        if mode == "train" and self.graph_probe and not self.use_graph:
+        if want_probe:
             probe = self.probe_graph(nxt, steps, dt, dt_local, issue_ms)
             nxt += 4 + steps
             if probe.get("use_graph"):
                 dt, dt_local = probe["dt"], probe["dt_local"]
         self.use_graph = False         # (events cannot be recorded inside a captured graph: the per-kernel timers run on eager steps)
         rec = self.ctx.rank == 0       # every rank runs the instrumented steps (they contain the gradient all-reduce); rank 0 records
-        if mode == "frame":
+        if not full:
+            timing, flops_per_step = {}, 0.0
+        elif mode == "frame":
             import torch
 
             def eager(_i):
@@ -835,15 +848,18 @@ def reference_call_sequence(ctx, args, steps=None):
     return out
 
 
-def collective_proof(ctx, wl, dt_local):
-    """What the collective itself saw (N > 1, or the forced one-rank RCCL group): an all-reduce of ones, every rank's own ms per step,
-    and the time of the step's ONE data-path collective (the all-reduce of the flat gradient bucket) from HIP events around it."""
+def collective_proof(ctx, wl, dt_local, full=True):
+    """What the collective itself saw (N > 1, or the forced one-rank RCCL group): an all-reduce of ones and every rank's own ms per step;
+    ``full``: also the time of the step's ONE data-path collective (the all-reduce of the flat gradient bucket) from HIP events around
+    it, a few steps of the other all-reduce mode and the bit-for-bit comparison of the replicas."""
     import torch
     import torch.distributed as dist
     from endosurf_amd.parallel import allreduce_flat
     ones = torch.ones(1, device=ctx.dev)
     dist.all_reduce(ones)
     per_rank = ctx.gather_over_ranks(dt_local)
+    if not full:
+        return dict(ranks_seen_by_collective=int(round(float(ones.item()))), per_rank_seconds=per_rank)
     flat = torch.zeros(wl.eng.n_param, device=ctx.dev)
     for _ in range(3):
         allreduce_flat(flat, force=True)
@@ -961,9 +977,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also measure everything else the line can carry: the same step with the marching "
+                         "early exit, host issue time, per-kernel timers and roofline, HBM accounting, collective timings (N > 1), the CPU "
+                         "baseline and the extras (other configurations, forward only, split precision, the reference call sequence). "
+                         "Without it the run sets up, warms up, times --steps steps and prints the line")
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS), help="BASELINE.json configuration (2 = the metric's)")
     ap.add_argument("--rays", type=int, default=None, help="override the configuration's rays per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--mode", default=None, choices=["train", "forward", "frame"])
     ap.add_argument("--refseq-only", choices=["plain", "logging", "flat_adam"], default=None,
                     help="profiling aid: run ONLY the reference trainer's own loop through the drop-in (ReferenceLoop) and print its record")
@@ -971,9 +992,9 @@ def main():
     ap.add_argument("--schedule", default="fused", choices=["fused", "plain"])
     ap.add_argument("--no-defer-eod", action="store_true", help="--refseq-only: render_cfg['defer_errorondepth'] = False (A/B of the deferred errorondepth evaluation)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="skip the extra early-exit timing and the extras (profiling runs: every launch of the process then belongs to the "
-                         "headline workload)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra lines (forward / split precision / cfg3 / cfg4 / cfg5 frame)")
+                    help="--full: skip the extra early-exit timing and the extras (profiling runs: every launch of the process then belongs to "
+                         "the headline workload)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the extra lines (forward / split precision / cfg3 / cfg4 / cfg5 frame)")
     ap.add_argument("--extras-timeout", type=float, default=420.0, help="watchdog: seconds the extras may take before the line is printed without them")
     ap.add_argument("--split-precision", action="store_true",
                     help="OPT-IN extra line, never the headline: large no-grad SDF queries and the weight-gradient GEMMs on the bf16 matrix "
@@ -1044,8 +1065,8 @@ def main():
                   frame_graph=not args.no_graph)
     wl.dump_dir = args.dump_outputs
     wl.graph_probe = (world > 1 or args.graph_probe) and wl.mode == "train" and not args.graph and not args.split_precision
-    m = wl.measure(args.warmup, args.steps, early_exit_extra=not args.headline_only)
-    proof = collective_proof(ctx, wl, m["dt_local"]) if dist_on else None
+    m = wl.measure(args.warmup, args.steps, early_exit_extra=not args.headline_only, full=args.full)
+    proof = collective_proof(ctx, wl, m["dt_local"], full=args.full) if dist_on else None
     probe = m.get("graph_probe")
     # per-rank diagnostics of a cold N > 1 run, gathered once (every rank contributes; rank 0 prints)
     per_rank = ctx.gather_obj(dict(rank=rank, host_issue_ms=m["host_issue_ms"], affinity=affinity,
@@ -1055,7 +1076,7 @@ def main():
     if rank == 0:
         per_rank_ms = [s / args.steps * 1e3 for s in proof["per_rank_seconds"]] if proof else [m["dt_local"] / args.steps * 1e3]
         out = dict(metric=wl.metric(), value=m["value"], unit="rays/s", n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=m["ms"],
-                   higher_is_better=True, scaling="strong" if mode == "frame" else "weak", vs_baseline=None,
+                   full=bool(args.full), higher_is_better=True, scaling="strong" if mode == "frame" else "weak", vs_baseline=None,
                    dtype="f32" if not args.split_precision else "f32 (OPT-IN split precision: large SDF queries, the point-evaluation chains and the "
                                                                 "weight-gradient GEMMs as 3 x bf16 planes, 6 partial products, fp32 accumulate; not the "
                                                                 "headline configuration)",
@@ -1075,8 +1096,8 @@ def main():
                                weights="reference init, torch.manual_seed(0)", algorithmic_gflop_per_ray=algorithmic_gflop_per_ray(cfg)),
                    ms_per_step_min=min(per_rank_ms), ms_per_step_max=max(per_rank_ms),
                    ranks_seen_by_collective=proof["ranks_seen_by_collective"] if proof else None,
-                   allreduce_ms=proof["allreduce_ms"] if proof else None,
-                   collective_proof=({k: v for k, v in proof.items() if k != "per_rank_seconds"} if proof else None),
+                   allreduce_ms=proof.get("allreduce_ms") if proof else None,
+                   collective_proof=({k: v for k, v in proof.items() if k != "per_rank_seconds"} if proof and args.full else None),
                    host_issue_ms=m["host_issue_ms"], sum_timed_kernel_ms=m["sum_timed_kernel_ms"],
                    host_issue_ms_min=min(r["host_issue_ms"] for r in per_rank) if per_rank[0]["host_issue_ms"] is not None else None,
                    host_issue_ms_max=max(r["host_issue_ms"] for r in per_rank) if per_rank[0]["host_issue_ms"] is not None else None,
@@ -1088,19 +1109,25 @@ def main():
                    per_rank=per_rank,
                    host_note="host_issue_ms: CPU time to enqueue one step into an empty queue (median of 5); sum_timed_kernel_ms: the MLP chain / "
                              "query / weight-gradient launches of one step (HIP events; the two front-end chains of a training step overlap)",
-                   roofline=wl.roofline(m), kernel_ms_per_step=timing.get("per_step_ms"), kernel_symbols=timing.get("symbols"),
+                   roofline=wl.roofline(m) if args.full else None, kernel_ms_per_step=timing.get("per_step_ms"), kernel_symbols=timing.get("symbols"),
                    kernel_launch_groups=timing.get("launch_groups"),
-                   hbm_accounting=(hbm_accounting(wl.n_rays * wl.S, 3 * wl.n_rays) if (args.config == 2 and mode == "train" and not args.rays
+                   hbm_accounting=(hbm_accounting(wl.n_rays * wl.S, 3 * wl.n_rays) if (args.full and args.config == 2 and mode == "train" and not args.rays
                                                                                        and not args.split_precision and args.schedule == "fused") else None),
                    hbm_accounting_note="algorithmic HBM bytes per launch (bench.py HBM_BYTES_PER_POINT: every saved stack written once / read once, "
                                        "per point, x the points of the launch) beside the rocprofv3 traffic of the same symbol from the committed PMC "
                                        "summary (FETCH_SIZE x 2 + WRITE_SIZE); ratio = measured / algorithmic",
                    cpu_baseline=None, extras=None)
     headline_is_default = args.config == 2 and mode == "train" and not args.split_precision and not args.rays
-    want_extras = headline_is_default and not (args.no_extras or args.headline_only)
+    want_extras = args.full and headline_is_default and not (args.no_extras or args.headline_only)
     wl.close()
+    if not args.full:          # the plain run ends here: set-up, warm-up, the timed steps, the line
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist_on:
+            torch.distributed.destroy_process_group()
+        return
 
-    # ---- after the headline, outside every timed region: the CPU baseline (rank 0 at N = 1) and the extras -------------------------
+    # ---- --full: after the headline, outside every timed region: the CPU baseline (rank 0 at N = 1) and the extras ----------------
     # A watchdog prints the line without the unfinished part if that section hangs (an RCCL collective with a missing rank would block for
     # minutes): the headline above is never at the mercy of an extra.
     import threading

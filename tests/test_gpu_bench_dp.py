@@ -26,7 +26,7 @@ def test_bench_two_ranks_one_gpu(mode):
     env = dict(os.environ, ES_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2" if mode == "train" else "1",
-           "--warmup", "1" if mode == "train" else "0", "--no-cpu-baseline", "--mode", mode]          # (a frame step = 327 680 rays: one is enough)
+           "--warmup", "1" if mode == "train" else "0", "--full", "--no-cpu-baseline", "--mode", mode]          # (a frame step = 327 680 rays: one is enough)
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -37,7 +37,7 @@ def test_bench_two_ranks_one_gpu(mode):
     assert d["ranks_seen_by_collective"] == 2 and 0 < d["ms_per_step_min"] <= d["ms_per_step_max"] and d["allreduce_ms"] > 0
     if mode == "train":
         assert d["scaling"] == "weak" and d["config"]["parallelism"] == "dp2" and d["roofline"]["frac"] > 0
-        # the default workload at N > 1 appends the multi-GPU configurations of BASELINE.json as extras
+        # the default workload at N > 1 with --full appends the multi-GPU configurations of BASELINE.json as extras
         ex = d["extras"]
         assert set(ex) >= {"cfg4", "cfg5_frame"} and "forward" not in ex, ex.keys()
         for k in ("cfg4", "cfg5_frame"):
@@ -61,7 +61,7 @@ def test_bench_many_ranks_one_gpu_cold_run_kit():
     env = dict(os.environ, ES_DIST_BACKEND="gloo", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--rays", "64", "--headline-only"]
+           "--full", "--no-cpu-baseline", "--rays", "64", "--headline-only"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500, cwd=REPO)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -95,7 +95,7 @@ def test_bench_self_launches_without_torchrun():
     """``python bench.py --gpus 2`` with no RANK / WORLD_SIZE in the environment must start its own ranks (VERDICT r1 #2)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["ES_DIST_BACKEND"] = "gloo"
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -106,16 +106,40 @@ def test_bench_self_launches_without_torchrun():
     assert d["ranks_seen_by_collective"] == 2
 
 
-def test_bench_default_line_carries_extras():
-    """The ONE command the driver runs (``python bench.py``; here with fewer steps and without the CPU baseline) prints the headline AND
-    every other number the builder reports: forward-only, split-precision training, cfg3, cfg4, one cfg5 frame (VERDICT r3 #1)."""
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+def test_bench_plain_line_is_lean():
+    """``python bench.py --gpus 1 --steps N --warmup W`` sets up, warms up, times the N steps and prints the headline: nothing else is
+    measured (every other section of the line is empty, ``full`` says so), and the whole process spends less than 30 s outside its steps."""
+    import time
+    steps, warmup = 5, 2
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)]
+    t0 = time.perf_counter()
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO)
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == steps and d["warmup"] == warmup and d["n_gpus"] == 1
+    assert d["metric"] == "training rays/sec (1024 rays x 64 samples)" and d["unit"] == "rays/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] * 1e-3 - 1024) < 1e-6 * 1024
+    assert d["config"]["baseline_config"] == 2 and d["config"]["with_early_exit"] is None
+    for k in ("cpu_baseline", "extras", "roofline", "kernel_ms_per_step", "kernel_symbols", "kernel_launch_groups", "hbm_accounting", "host_issue_ms",
+              "sum_timed_kernel_ms", "graph_probe", "collective_proof", "ranks_seen_by_collective"):
+        assert d[k] is None, (k, d[k])
+    assert wall - (steps + warmup) * d["ms_per_step"] * 1e-3 < 30.0, wall
+
+
+def test_bench_full_line_carries_extras():
+    """``python bench.py --full`` (here with fewer steps and without the CPU baseline) prints the headline AND every other number the
+    builder reports: forward-only, split-precision training, cfg3, cfg4, one cfg5 frame (VERDICT r3 #1)."""
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=REPO)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
     d = json.loads(lines[0])
     assert d["config"]["baseline_config"] == 2 and d["dtype"] == "f32" and d["n_gpus"] == 1 and d["ranks_seen_by_collective"] is None
+    assert d["full"] is True and d["roofline"]["frac"] > 0 and d["host_issue_ms"] > 0 and d["config"]["with_early_exit"]["value"] > 0
     ex = d["extras"]
     assert set(ex) == {"reference_call_sequence", "forward", "split_precision_train", "cfg3", "cfg4", "cfg5_frame"}, ex.keys()
     # the reference trainer's own loop through the drop-in (VERDICT r5 #1): without and with its logging traffic; from its second step
@@ -166,7 +190,7 @@ def test_bench_dump_outputs_same_inputs_every_run(tmp_path):
 @pytest.mark.parametrize("config", [3, 4])
 def test_bench_other_baseline_configs(config):
     """--config 3 (2048 rays x 128 samples) and --config 4 (use_deform False) run and report a roofline."""
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--config", str(config), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--config", str(config), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=REPO)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -333,7 +357,7 @@ def test_bench_rccl_world1_line():
     env = {k: v for k, v in os.environ.items() if k != "ES_DIST_BACKEND"}
     env["ES_FORCE_DIST"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

@@ -6,7 +6,7 @@ R=${1:-3}; shift
 for r in $(seq $R); do
   for v in ${VARIANTS:-A B}; do
     cp $L/variant_$v.so $L/libendosurf_hip.so
-    python bench.py --no-cpu-baseline --headline-only --steps 30 --warmup 5 "$@" 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --headline-only --steps 30 --warmup 5 "$@" 2>/dev/null | python -c "
 import json,sys
 b=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v', round(b['ms_per_step'],3), round(b['value']), {s['kernel']:s['ms_per_step'] for s in b['kernel_symbols'] if True})"
   done

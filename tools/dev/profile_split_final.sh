@@ -1,8 +1,8 @@
 set -u
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R; mkdir -p gpurun_out profiles
-python bench.py --split-precision --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > profiles/r03_split.json
-python bench.py --config 3 --split-precision --steps 15 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > profiles/r03_cfg3_split.json
-python bench.py --config 4 --split-precision --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > profiles/r03_cfg4_split.json
+python bench.py --full --split-precision --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > profiles/r03_split.json
+python bench.py --full --config 3 --split-precision --steps 15 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > profiles/r03_cfg3_split.json
+python bench.py --full --config 4 --split-precision --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > profiles/r03_cfg4_split.json
 bash tools/dev/profile_mode.sh r03_split --split-precision > gpurun_out/prof_split.log 2>&1
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_split_stats -o train -- python $R/bench.py --no-cpu-baseline --headline-only --split-precision --steps 10 --warmup 2 > /dev/null 2>&1

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out/wgpair_$1
 mkdir -p $O
-B="python $R/bench.py --no-cpu-baseline --headline-only"
+B="python $R/bench.py --full --no-cpu-baseline --headline-only"
 $B --steps 20 --warmup 4 | tail -1 > $R/gpurun_out/wgpair_$1.json
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O -o p -- $B --steps 2 --warmup 1 > /dev/null 2>&1
 python - <<PY

@@ -26,7 +26,7 @@ python bench.py --refseq-only plain --steps 30 --warmup 5 | tail -1 > profiles/$
 python bench.py --refseq-only logging --steps 30 --warmup 5 | tail -1 > profiles/${TAG}_plain_logging_bench.json
 cp $(find $O/stats -name "*kernel_stats.csv" | head -1) profiles/${TAG}_train_kernel_stats.csv
 python tools/pmc_summary.py $TAG $(dirname $(find $O/pmcA -name "*counter_collection.csv" | head -1)) $(dirname $(find $O/pmcB -name "*counter_collection.csv" | head -1)) $(dirname $(find $O/pmcC -name "*counter_collection.csv" | head -1)) | head -14
-python bench.py --steps 30 --warmup 5 | tail -1 > profiles/${TAG}_bench.json
+python bench.py --full --steps 30 --warmup 5 | tail -1 > profiles/${TAG}_bench.json
 cp profiles/${TAG}_train_kernel_stats.csv profiles/${TAG}_pmc_summary.json profiles/${TAG}_bench.json profiles/${TAG}_plain_kernel_stats.csv profiles/${TAG}_plain_bench.json profiles/${TAG}_plain_logging_bench.json gpurun_out/
 head -c 600 profiles/${TAG}_bench.json
 rm -rf $O
