@@ -1,0 +1,736 @@
+// Mesh clean-up and geometric error on the device (ABI v11): what the reference's demo does to an extracted mesh through Open3D on the
+// host (trainer_endosurf.py:436-447 cluster_connected_triangles + remove_triangles_by_mask, :418 / :452ff point-cloud distance), as two
+// primitives.  Numpy twins: endosurf_amd/meshing.py mesh_components / keep_components / nearest.  Contract: DESIGN.md 7b.
+//
+// Connected components (vertex connectivity; label = the smallest vertex index of the component):
+//   k_mesh_init          parent[v] = v
+//   k_mesh_hook          per non-degenerate triangle: m = min of its corners' parents; parent[r] = min(parent[r], m) for the others
+//   k_mesh_jump          parent[v] = the ancestor reached by at most MESH_WALK links; a pass shortens every path 32-fold, so
+//                        ceil(log2 V / 5) passes (the host launches exactly that many) leave the forest flat
+//   k_mesh_label         triangle_label, component_triangles (one integer add per distinct label of a wave), the degenerate count
+//   k_mesh_stats         components with a triangle, the largest triangle count
+//   k_mesh_keep_flags    triangle kept / vertex used bytes (the fp64 comparison of the reference's numpy line)
+//   k_mesh_keep_blocksum / k_mesh_scan_blocks / k_mesh_keep_offsets / k_mesh_keep_emit   iso.hip's stable compaction over the two flags
+// Nearest neighbour (exact; fp32 squared distance (dx dx + dy dy) + dz dz without contraction, ties to the smallest index):
+//   k_nn_bbox / k_nn_header     box of the finite points -> the grid (at most one cell per four finite points, at least one per axis)
+//   k_nn_count / k_mesh_scan_* / k_nn_fill   counting sort of the points by cell (z fastest) into (x, y, z, index) records
+//   k_nn_query           one thread per query: Chebyshev shells around the query's (clamped) cell until the stop rule proves the rest away
+//
+// Integer atomics, and why no result depends on their order: atomicMin on parent[] (a round's outcome may differ from call to call,
+// the fixed point -- every vertex at the smallest index of its component -- cannot), atomicOr on the round's ``changed`` word,
+// atomicAdd of counts (component_triangles, the totals, the cell histogram), atomicMax of the largest count, and atomicAdd on a
+// cell's fill cursor (it orders the records inside a cell, which the query's (distance, index) minimum does not see).  No float
+// atomics.  No workgroup waits for another one; the loop over rounds is on the host; every device loop is bounded by an argument
+// or a constant, and every index read from a buffer is range-checked before it addresses memory, whatever the scratch holds.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/endosurf_hip.h"
+#include "launch.h"
+#include "scan.h"
+
+namespace es {
+
+constexpr int MESH_PER_THREAD = 16;                          // consecutive items of one thread of the scan kernels
+constexpr int MESH_CHUNK = 256 * MESH_PER_THREAD;            // items per scan workgroup
+constexpr long long MESH_MAX = 1ll << 31;                    // int32 indices
+constexpr unsigned MESH_MAX_GRID = 1u << 16;                 // grid-stride launches
+constexpr int MESH_WALK = 32;                                // links one thread of k_mesh_jump follows
+constexpr int NN_PARTS = 1024;                               // workgroups of the bounding-box reduction
+constexpr int NN_PER_CELL = 4;                               // finite points per cell the grid aims for
+
+static inline long long mesh_up16(long long b) { return (b + 15) / 16 * 16; }
+static inline unsigned mesh_grid(long long n) {
+    const long long wg = (n + 255) / 256;
+    return (unsigned)(wg < 1 ? 1 : (wg < MESH_MAX_GRID ? wg : MESH_MAX_GRID));
+}
+static inline int mesh_jump_passes(long long V) {
+    int bits = 0;
+    while ((1ll << bits) < V) ++bits;                        // ceil(log2 V)
+    return bits < 5 ? 1 : (bits + 4) / 5;
+}
+
+struct MeshScratch {
+    int* parent;             // [V] the hook-and-jump forest; flat between rounds
+    int* voff;               // [V] exclusive scan of vflag
+    int* toff;               // [T] exclusive scan of tflag
+    int* bsum;               // [nblk][2] used vertices / kept triangles of a chunk
+    int* boff;               // [nblk][2] exclusive scan of bsum
+    unsigned char* vflag;    // [V] vertex survives the filter
+    unsigned char* tflag;    // [T] triangle survives the filter
+    long long nblk;
+};
+static inline long long mesh_nblk(long long V, long long T) {
+    const long long n = V > T ? V : T;
+    return n > 0 ? (n + MESH_CHUNK - 1) / MESH_CHUNK : 1;
+}
+static inline long long mesh_scratch_bytes(long long V, long long T) {
+    return 2 * mesh_up16(4 * V) + mesh_up16(4 * T) + 2 * mesh_up16(8 * mesh_nblk(V, T)) + mesh_up16(V) + mesh_up16(T) + 16;
+}
+static inline MeshScratch mesh_carve(void* scratch, long long V, long long T) {
+    MeshScratch s;
+    s.nblk = mesh_nblk(V, T);
+    char* p = static_cast<char*>(scratch);
+    s.parent = reinterpret_cast<int*>(p); p += mesh_up16(4 * V);
+    s.voff = reinterpret_cast<int*>(p); p += mesh_up16(4 * V);
+    s.toff = reinterpret_cast<int*>(p); p += mesh_up16(4 * T);
+    s.bsum = reinterpret_cast<int*>(p); p += mesh_up16(8 * s.nblk);
+    s.boff = reinterpret_cast<int*>(p); p += mesh_up16(8 * s.nblk);
+    s.vflag = reinterpret_cast<unsigned char*>(p); p += mesh_up16(V);
+    s.tflag = reinterpret_cast<unsigned char*>(p);
+    return s;
+}
+
+__device__ __forceinline__ bool in_range(int i, int n) { return (unsigned)i < (unsigned)n; }
+// a triangle takes part: three different corners, all of them vertices
+__device__ __forceinline__ bool tri_load(const int* __restrict__ tris, long long t, int V, int& a, int& b, int& c) {
+    a = tris[3 * t]; b = tris[3 * t + 1]; c = tris[3 * t + 2];
+    return in_range(a, V) && in_range(b, V) && in_range(c, V) && a != b && b != c && a != c;
+}
+__device__ __forceinline__ int min3(int a, int b, int c) { return min(a, min(b, c)); }
+
+__global__ __launch_bounds__(256) void k_mesh_init(int* __restrict__ parent, int V) {
+    for (long long v = blockIdx.x * 256ll + threadIdx.x; v < V; v += gridDim.x * 256ll) parent[v] = (int)v;
+}
+
+__global__ __launch_bounds__(256) void k_mesh_hook(const int* __restrict__ tris, int V, long long T, int* parent, int* changed) {
+    bool ch = false;
+    for (long long t = blockIdx.x * 256ll + threadIdx.x; t < T; t += gridDim.x * 256ll) {
+        int a, b, c;
+        if (!tri_load(tris, t, V, a, b, c)) continue;
+        const int ra = parent[a], rb = parent[b], rc = parent[c];
+        if (!in_range(ra, V) || !in_range(rb, V) || !in_range(rc, V)) continue;          // (a forest es_mesh_cc_begin did not make)
+        const int m = min3(ra, rb, rc);
+        if (ra != m) { atomicMin(parent + ra, m); ch = true; }
+        if (rb != m) { atomicMin(parent + rb, m); ch = true; }
+        if (rc != m) { atomicMin(parent + rc, m); ch = true; }
+    }
+    if (__syncthreads_or(ch) && threadIdx.x == 0) atomicOr(changed, 1);
+}
+
+// parent[x] <= x always, so a path has fewer than V links.  A thread reads links other threads are shortening: whatever it reads is
+// an ancestor at least as far as the link it replaces, so MESH_WALK reads climb MESH_WALK old links or reach the root, and after the
+// pass every path is at most ceil(old length / MESH_WALK) long.
+__global__ __launch_bounds__(256) void k_mesh_jump(int* parent, int V) {
+    for (long long v = blockIdx.x * 256ll + threadIdx.x; v < V; v += gridDim.x * 256ll) {
+        int p = parent[v];
+        if (p == (int)v || !in_range(p, V)) continue;
+        for (int i = 0; i < MESH_WALK; ++i) {
+            const int pp = parent[p];
+            if (pp == p || !in_range(pp, V)) break;
+            p = pp;
+        }
+        parent[v] = p;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_mesh_label(const int* __restrict__ tris, int V, long long T, const int* __restrict__ parent,
+                                                    int* __restrict__ triangle_label, int* component_triangles, unsigned long long* totals) {
+    __shared__ int part[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int n_deg = 0;
+    for (long long base = blockIdx.x * 256ll; base < T; base += gridDim.x * 256ll) {          // (wave-uniform trip count)
+        const long long t = base + threadIdx.x;
+        int lab = -1;
+        if (t < T) {
+            int a, b, c;
+            if (tri_load(tris, t, V, a, b, c)) lab = parent[a];
+            if (!in_range(lab, V)) lab = -1;
+            triangle_label[t] = lab;
+            n_deg += lab < 0 ? 1 : 0;
+        }
+        // one add per distinct label of the wave; every turn retires its leader, so there are at most 64 turns
+        unsigned long long todo = __ballot(lab >= 0);
+        for (int turn = 0; turn < 64 && todo; ++turn) {
+            const int leader = __ffsll((long long)todo) - 1;
+            const int l0 = __shfl(lab, leader, 64);
+            const unsigned long long same = __ballot(lab == l0) & todo;
+            if (lane == leader) atomicAdd(component_triangles + l0, (int)__popcll(same));
+            todo &= ~same;
+        }
+    }
+    n_deg = wscan_add(n_deg, lane);
+    if (lane == 63) part[wv] = n_deg;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int n = part[0] + part[1] + part[2] + part[3];
+        if (n) atomicAdd(totals + 2, (unsigned long long)n);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_mesh_stats(const int* __restrict__ component_triangles, int V, unsigned long long* totals) {
+    __shared__ int part[4][2];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int n = 0, mx = 0;
+    for (long long v = blockIdx.x * 256ll + threadIdx.x; v < V; v += gridDim.x * 256ll) {
+        const int c = component_triangles[v];
+        n += c > 0 ? 1 : 0;
+        mx = max(mx, c);
+    }
+    n = wscan_add(n, lane);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) mx = max(mx, __shfl_xor(mx, o, 64));
+    if (lane == 63) { part[wv][0] = n; part[wv][1] = mx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int ns = part[0][0] + part[1][0] + part[2][0] + part[3][0];
+        const int ms = max(max(part[0][1], part[1][1]), max(part[2][1], part[3][1]));
+        if (ns) atomicAdd(totals, (unsigned long long)ns);
+        if (ms) atomicMax(totals + 1, (unsigned long long)ms);
+    }
+}
+
+// kept = not degenerate and not (count of its component < keep_ratio x the largest count), in fp64 like numpy's int64 < float64
+__global__ __launch_bounds__(256) void k_mesh_keep_flags(const int* __restrict__ tris, int V, long long T, const int* __restrict__ triangle_label,
+                                                         const int* __restrict__ component_triangles, double limit, int compact,
+                                                         unsigned char* __restrict__ tflag, unsigned char* vflag) {
+    for (long long t = blockIdx.x * 256ll + threadIdx.x; t < T; t += gridDim.x * 256ll) {
+        int a, b, c;
+        const bool ok = tri_load(tris, t, V, a, b, c);
+        const int lab = triangle_label[t];
+        const bool keep = ok && in_range(lab, V) && !((double)component_triangles[lab] < limit);
+        tflag[t] = keep ? 1 : 0;
+        if (keep && compact) { vflag[a] = 1; vflag[b] = 1; vflag[c] = 1; }          // (every writer stores the same byte)
+    }
+}
+
+// 16 consecutive flags of a thread (0 beyond n) -> how many are set
+__device__ __forceinline__ void flags_load(const unsigned char* __restrict__ f, long long n, long long i0, unsigned char (&c)[MESH_PER_THREAD]) {
+    if (i0 + MESH_PER_THREAD <= n) {
+        const uint4 w = *reinterpret_cast<const uint4*>(f + i0);          // 16-byte aligned: f is, i0 a multiple of 16
+        __builtin_memcpy(c, &w, sizeof(c));
+    } else {
+#pragma unroll
+        for (int i = 0; i < MESH_PER_THREAD; ++i) c[i] = i0 + i < n ? f[i0 + i] : (unsigned char)0;
+    }
+}
+__device__ __forceinline__ int flags_sum(const unsigned char (&c)[MESH_PER_THREAD]) {
+    int n = 0;
+#pragma unroll
+    for (int i = 0; i < MESH_PER_THREAD; ++i) n += c[i] ? 1 : 0;
+    return n;
+}
+
+__global__ __launch_bounds__(256) void k_mesh_keep_blocksum(const unsigned char* __restrict__ vflag, long long V, const unsigned char* __restrict__ tflag,
+                                                            long long T, int* __restrict__ bsum) {
+    __shared__ int part[4][2];
+    unsigned char cv[MESH_PER_THREAD], ct[MESH_PER_THREAD];
+    const long long i0 = (long long)blockIdx.x * MESH_CHUNK + threadIdx.x * MESH_PER_THREAD;
+    flags_load(vflag, V, i0, cv);
+    flags_load(tflag, T, i0, ct);
+    int nv = flags_sum(cv), nt = flags_sum(ct);
+    int total[2];
+    block_scan2(nv, nt, part, total);
+    if (threadIdx.x == 0) { bsum[2 * (size_t)blockIdx.x] = total[0]; bsum[2 * (size_t)blockIdx.x + 1] = total[1]; }
+}
+
+// iso.hip k_iso_scan_blocks: one workgroup, thread i owns a contiguous run of chunks; 64-bit sums, stored truncated
+__global__ __launch_bounds__(256) void k_mesh_scan_blocks(const int* __restrict__ bsum, long long nblk, int* __restrict__ boff, long long* __restrict__ totals) {
+    __shared__ long long part[4][2];
+    const long long per = (nblk + 255) / 256, b0 = threadIdx.x * per, b1 = b0 + per < nblk ? b0 + per : nblk;
+    long long sv = 0, st = 0;
+    for (long long b = b0; b < b1; ++b) { sv += bsum[2 * b]; st += bsum[2 * b + 1]; }
+    long long total[2];
+    block_scan2(sv, st, part, total);
+    for (long long b = b0; b < b1; ++b) {
+        boff[2 * b] = (int)sv; boff[2 * b + 1] = (int)st;
+        sv += bsum[2 * b]; st += bsum[2 * b + 1];
+    }
+    if (threadIdx.x == 0 && totals) { totals[0] = total[0]; totals[1] = total[1]; }
+}
+
+__global__ __launch_bounds__(256) void k_mesh_keep_offsets(const unsigned char* __restrict__ vflag, long long V, const unsigned char* __restrict__ tflag,
+                                                           long long T, const int* __restrict__ boff, int* __restrict__ voff, int* __restrict__ toff) {
+    __shared__ int part[4][2];
+    unsigned char cv[MESH_PER_THREAD], ct[MESH_PER_THREAD];
+    const long long i0 = (long long)blockIdx.x * MESH_CHUNK + threadIdx.x * MESH_PER_THREAD;
+    flags_load(vflag, V, i0, cv);
+    flags_load(tflag, T, i0, ct);
+    int nv = flags_sum(cv), nt = flags_sum(ct);
+    int total[2];
+    block_scan2(nv, nt, part, total);
+    nv += boff[2 * (size_t)blockIdx.x]; nt += boff[2 * (size_t)blockIdx.x + 1];
+#pragma unroll
+    for (int i = 0; i < MESH_PER_THREAD; ++i) {
+        if (i0 + i < V) voff[i0 + i] = nv;
+        if (i0 + i < T) toff[i0 + i] = nt;
+        nv += cv[i] ? 1 : 0; nt += ct[i] ? 1 : 0;
+    }
+}
+
+// Every write is checked against the capacity of its output buffer, every index against V.
+__global__ __launch_bounds__(256) void k_mesh_keep_emit(const float* __restrict__ verts, const int* __restrict__ tris, int V, long long T,
+                                                        const int* __restrict__ voff, const int* __restrict__ toff,
+                                                        const unsigned char* __restrict__ vflag, const unsigned char* __restrict__ tflag, int cap_v,
+                                                        int cap_t, float* __restrict__ verts_out, int* __restrict__ tris_out,
+                                                        long long* __restrict__ vertex_map) {
+    const long long n = V > T ? V : T;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += gridDim.x * 256ll) {
+        if (i < V && vflag[i]) {
+            const int o = voff[i];
+            if (in_range(o, cap_v)) {
+                if (verts_out) {
+                    verts_out[3 * (size_t)o] = verts[3 * i]; verts_out[3 * (size_t)o + 1] = verts[3 * i + 1]; verts_out[3 * (size_t)o + 2] = verts[3 * i + 2];
+                }
+                if (vertex_map) vertex_map[o] = i;
+            }
+        }
+        if (i < T && tflag[i]) {
+            const int o = toff[i];
+            if (in_range(o, cap_t)) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const int v = tris[3 * i + j];
+                    tris_out[3 * (size_t)o + j] = in_range(v, V) ? voff[v] : -1;
+                }
+            }
+        }
+    }
+}
+
+// ---- nearest neighbour ----------------------------------------------------------------------------------------------------------------
+
+struct NnHeader {            // 64 bytes at the start of the scratch, written by k_nn_header
+    float lo[3];             // the box of the finite points (exact minima / maxima)
+    float hi[3];
+    float inv_h[3];          // cells per unit length along each axis (0 for an axis of one cell)
+    float h_safe;            // a lower bound of the width of every cell of an axis that has more than one (the stop rule's h)
+    int n[3];                // cells per axis, >= 1, n[0] n[1] n[2] <= max(1, finite points / NN_PER_CELL)
+    int n_finite;
+    int pad[2];
+};
+struct NnScratch {
+    NnHeader* head;
+    float* part;             // [NN_PARTS][8] lo, hi, finite count (as int bits) of a workgroup's points
+    int* cell;               // [P] cell of each point, -1 for a non-finite one
+    int* count;              // [P + 1] points per cell, then (k_nn_offsets) unused
+    int* cursor;             // [P + 1] fill cursor of each cell (zeroed with count)
+    int* start;              // [P + 1] first record of each cell; start[cells .. P] = finite points
+    int* bsum;               // [nblk][2]
+    int* boff;               // [nblk][2]
+    float4* rec;             // [P] (x, y, z, index) sorted by cell
+    long long nblk;
+};
+static inline long long nn_scratch_bytes(long long P) {
+    const long long nblk = (P + 1 + MESH_CHUNK - 1) / MESH_CHUNK;
+    return 64 + mesh_up16(32ll * NN_PARTS) + mesh_up16(4 * P) + 3 * mesh_up16(4 * (P + 1)) + 2 * mesh_up16(8 * nblk) + 16 * P + 16;
+}
+static inline NnScratch nn_carve(void* scratch, long long P) {
+    NnScratch s;
+    s.nblk = (P + 1 + MESH_CHUNK - 1) / MESH_CHUNK;
+    char* p = static_cast<char*>(scratch);
+    s.head = reinterpret_cast<NnHeader*>(p); p += 64;
+    s.part = reinterpret_cast<float*>(p); p += mesh_up16(32ll * NN_PARTS);
+    s.cell = reinterpret_cast<int*>(p); p += mesh_up16(4 * P);
+    s.count = reinterpret_cast<int*>(p); p += mesh_up16(4 * (P + 1));
+    s.cursor = reinterpret_cast<int*>(p); p += mesh_up16(4 * (P + 1));
+    s.start = reinterpret_cast<int*>(p); p += mesh_up16(4 * (P + 1));
+    s.bsum = reinterpret_cast<int*>(p); p += mesh_up16(8 * s.nblk);
+    s.boff = reinterpret_cast<int*>(p); p += mesh_up16(8 * s.nblk);
+    s.rec = reinterpret_cast<float4*>(p);
+    return s;
+}
+
+__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+
+__global__ __launch_bounds__(256) void k_nn_bbox(const float* __restrict__ pts, long long P, float* __restrict__ part) {
+    __shared__ float red[4][6];
+    __shared__ int cnt[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    int n = 0;
+    for (long long p = blockIdx.x * 256ll + threadIdx.x; p < P; p += gridDim.x * 256ll) {
+        const float x = pts[3 * p], y = pts[3 * p + 1], z = pts[3 * p + 2];
+        if (!finite3(x, y, z)) continue;
+        lo[0] = fminf(lo[0], x); lo[1] = fminf(lo[1], y); lo[2] = fminf(lo[2], z);
+        hi[0] = fmaxf(hi[0], x); hi[1] = fmaxf(hi[1], y); hi[2] = fmaxf(hi[2], z);
+        ++n;
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], o, 64)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o, 64)); }
+        n += __shfl_xor(n, o, 64);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { red[wv][a] = lo[a]; red[wv][3 + a] = hi[a]; }
+        cnt[wv] = n;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        part[8 * (size_t)blockIdx.x + a] = fminf(fminf(red[0][a], red[1][a]), fminf(red[2][a], red[3][a]));
+        part[8 * (size_t)blockIdx.x + 3 + a] = fmaxf(fmaxf(red[0][3 + a], red[1][3 + a]), fmaxf(red[2][3 + a], red[3][3 + a]));
+    }
+    if (threadIdx.x == 3) part[8 * (size_t)blockIdx.x + 6] = __int_as_float(cnt[0] + cnt[1] + cnt[2] + cnt[3]);
+}
+
+// One workgroup: the box of all parts, then thread 0 lays out the grid.  Cells are cubes of edge h = (volume of the axes that get
+// more than one cell / target)^(1 / their number), n = floor(extent / h) per axis; an axis shorter than h gets one cell and leaves
+// the product, which is then <= target = finite points / NN_PER_CELL: a query that looks at the whole grid reads fewer cell bounds
+// than there are points.
+__global__ __launch_bounds__(256) void k_nn_header(const float* __restrict__ part, int nparts, NnHeader* __restrict__ head) {
+    __shared__ float red[4][6];
+    __shared__ long long cnt[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    long long n = 0;
+    for (int i = threadIdx.x; i < nparts; i += 256) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], part[8 * i + a]); hi[a] = fmaxf(hi[a], part[8 * i + 3 + a]); }
+        n += __float_as_int(part[8 * i + 6]);
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], o, 64)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o, 64)); }
+        n += __shfl_xor(n, o, 64);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { red[wv][a] = lo[a]; red[wv][3 + a] = hi[a]; }
+        cnt[wv] = n;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    NnHeader h;
+    const long long nf = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+    double ext[3];
+    for (int a = 0; a < 3; ++a) {
+        h.lo[a] = fminf(fminf(red[0][a], red[1][a]), fminf(red[2][a], red[3][a]));
+        h.hi[a] = fmaxf(fmaxf(red[0][3 + a], red[1][3 + a]), fmaxf(red[2][3 + a], red[3][3 + a]));
+        ext[a] = nf > 0 ? (double)h.hi[a] - (double)h.lo[a] : 0.0;
+        h.n[a] = 1;
+    }
+    const double target = (double)(nf / NN_PER_CELL > 1 ? nf / NN_PER_CELL : 1);
+    bool active[3] = {ext[0] > 0.0, ext[1] > 0.0, ext[2] > 0.0};
+    for (int it = 0; it < 3; ++it) {          // an axis shorter than the cell edge leaves the set; at most three turns change it
+        int k = 0;
+        double vol = 1.0;
+        for (int a = 0; a < 3; ++a) if (active[a]) { ++k; vol *= ext[a]; }
+        if (k == 0) break;
+        const double edge = k == 1 ? vol / target : (k == 2 ? sqrt(vol / target) : cbrt(vol / target));
+        bool again = false;
+        for (int a = 0; a < 3; ++a) {
+            h.n[a] = 1;
+            if (!active[a]) continue;
+            const double c = floor(ext[a] / edge);
+            if (!(c >= 2.0)) { active[a] = false; again = true; }
+            else h.n[a] = (int)(c < 1048576.0 ? c : 1048576.0);
+        }
+        if (!again) break;
+    }
+    for (int a = 0; a < 3; ++a) if (!active[a]) h.n[a] = 1;
+    if ((double)h.n[0] * h.n[1] * h.n[2] > target) h.n[0] = h.n[1] = h.n[2] = 1;          // (cannot happen; keeps the promise anyway)
+    float hs = INFINITY;
+    for (int a = 0; a < 3; ++a) {
+        const float e = h.hi[a] - h.lo[a];
+        h.inv_h[a] = h.n[a] > 1 ? (float)h.n[a] / e : 0.f;
+        // the fp32 cell function below moves a cell boundary by at most a few 2^-23 of the extent: 2^-9 of a cell covers 2^11 cells an axis
+        if (h.n[a] > 1) hs = fminf(hs, e / (float)h.n[a] * (1.f - 1.f / 512.f) - e * 4.8e-7f);
+    }
+    h.h_safe = (hs > 0.f && hs < INFINITY) ? hs : 0.f;
+    h.n_finite = (int)nf;
+    h.pad[0] = h.pad[1] = 0;
+    *head = h;
+}
+
+// the cell coordinate of x along one axis: non-decreasing in x, the same expression for points and queries
+__device__ __forceinline__ int nn_cell1(float x, float lo, float inv_h, int n) {
+    const float f = (x - lo) * inv_h;
+    if (!(f > 0.f)) return 0;                                     // (x <= lo, an axis of one cell, or inf x 0)
+    return f >= (float)(n - 1) ? n - 1 : (int)f;
+}
+// the header as a kernel may use it: dimensions that the buffers can hold, whatever the scratch held
+__device__ __forceinline__ bool nn_head_ok(const NnHeader& h, long long P) {
+    return h.n[0] >= 1 && h.n[1] >= 1 && h.n[2] >= 1 && (long long)h.n[0] * h.n[1] <= P && (long long)h.n[0] * h.n[1] * h.n[2] <= P;
+}
+
+__global__ __launch_bounds__(256) void k_nn_count(const float* __restrict__ pts, long long P, const NnHeader* __restrict__ head, int* __restrict__ cell,
+                                                  int* count) {
+    const NnHeader h = *head;
+    const bool ok = nn_head_ok(h, P);
+    for (long long p = blockIdx.x * 256ll + threadIdx.x; p < P; p += gridDim.x * 256ll) {
+        const float x = pts[3 * p], y = pts[3 * p + 1], z = pts[3 * p + 2];
+        int c = -1;
+        if (ok && finite3(x, y, z))
+            c = (nn_cell1(x, h.lo[0], h.inv_h[0], h.n[0]) * h.n[1] + nn_cell1(y, h.lo[1], h.inv_h[1], h.n[1])) * h.n[2] + nn_cell1(z, h.lo[2], h.inv_h[2], h.n[2]);
+        cell[p] = c;
+        if (c >= 0) atomicAdd(count + c, 1);
+    }
+}
+
+// exclusive scan of count[0 .. n) in iso.hip's three launches (second sequence unused)
+__device__ __forceinline__ void ints_load(const int* __restrict__ f, long long n, long long i0, int (&c)[MESH_PER_THREAD]) {
+#pragma unroll
+    for (int i = 0; i < MESH_PER_THREAD; ++i) c[i] = i0 + i < n ? f[i0 + i] : 0;
+}
+__global__ __launch_bounds__(256) void k_nn_blocksum(const int* __restrict__ count, long long n, int* __restrict__ bsum) {
+    __shared__ int part[4][2];
+    int c[MESH_PER_THREAD];
+    ints_load(count, n, (long long)blockIdx.x * MESH_CHUNK + threadIdx.x * MESH_PER_THREAD, c);
+    int s = 0, z = 0;
+#pragma unroll
+    for (int i = 0; i < MESH_PER_THREAD; ++i) s += c[i];
+    int total[2];
+    block_scan2(s, z, part, total);
+    if (threadIdx.x == 0) { bsum[2 * (size_t)blockIdx.x] = total[0]; bsum[2 * (size_t)blockIdx.x + 1] = 0; }
+}
+__global__ __launch_bounds__(256) void k_nn_offsets(const int* __restrict__ count, long long n, const int* __restrict__ boff, int* __restrict__ start) {
+    __shared__ int part[4][2];
+    int c[MESH_PER_THREAD];
+    const long long i0 = (long long)blockIdx.x * MESH_CHUNK + threadIdx.x * MESH_PER_THREAD;
+    ints_load(count, n, i0, c);
+    int s = 0, z = 0;
+#pragma unroll
+    for (int i = 0; i < MESH_PER_THREAD; ++i) s += c[i];
+    int total[2];
+    block_scan2(s, z, part, total);
+    s += boff[2 * (size_t)blockIdx.x];
+#pragma unroll
+    for (int i = 0; i < MESH_PER_THREAD; ++i) {
+        if (i0 + i < n) start[i0 + i] = s;
+        s += c[i];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_nn_fill(const float* __restrict__ pts, long long P, const int* __restrict__ cell, const int* __restrict__ start,
+                                                 int* cursor, float4* __restrict__ rec) {
+    for (long long p = blockIdx.x * 256ll + threadIdx.x; p < P; p += gridDim.x * 256ll) {
+        const int c = cell[p];
+        if (c < 0 || c >= P) continue;
+        const long long o = (long long)start[c] + atomicAdd(cursor + c, 1);
+        if (o < 0 || o >= P) continue;
+        rec[o] = make_float4(pts[3 * p], pts[3 * p + 1], pts[3 * p + 2], __int_as_float((int)p));
+    }
+}
+
+// (dx dx + dy dy) + dz dz with every product and sum rounded on its own: the library is built with -ffp-contract=fast, and a fused
+// multiply-add here would give other last bits than the numpy twin (and than a caller's own fp32 check)
+__device__ __forceinline__ float nn_dist2(float dx, float dy, float dz) {
+#pragma clang fp contract(off)
+    const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+    const float s = xx + yy;
+    return s + zz;
+}
+
+// The correctly rounded square root of x >= 0, whatever the accuracy of the device's sqrtf (measured: it is not numpy's): the
+// neighbour s -+ 1 ulp replaces s when x lies beyond the midpoint between them, decided exactly -- a midpoint has 25 significant bits,
+// so its square is exact in fp64.  Two turns cover a start that is 2 ulp off.
+__device__ __forceinline__ float nn_sqrt_rn(float x) {
+    float s = sqrtf(x);
+    const double xd = (double)x;
+    for (int turn = 0; turn < 2 && s > 0.f; ++turn) {
+        const float lo = __int_as_float(__float_as_int(s) - 1), hi = __int_as_float(__float_as_int(s) + 1);
+        const double m1 = 0.5 * ((double)lo + (double)s), m2 = 0.5 * ((double)s + (double)hi);
+        if (xd < m1 * m1) s = lo;
+        else if (xd > m2 * m2) s = hi;
+        else break;
+    }
+    return s;
+}
+
+// The records of cells [c0, c1] of one (x, y) column are contiguous (z fastest).  (d2, index) keeps the lexicographic minimum, so the
+// order of the records inside a cell does not show.
+__device__ __forceinline__ void nn_scan_run(const float4* __restrict__ rec, const int* __restrict__ start, long long P, int c0, int c1, float qx,
+                                            float qy, float qz, float& best, int& arg) {
+    long long s = start[c0], e = start[c1 + 1];
+    s = s < 0 ? 0 : s;
+    e = e > P ? P : e;
+    for (long long i = s; i < e; ++i) {
+        const float4 r = rec[i];
+        const float d2 = nn_dist2(qx - r.x, qy - r.y, qz - r.z);
+        const int id = __float_as_int(r.w);
+        if (d2 < best || (d2 == best && id < arg)) { best = d2; arg = id; }
+    }
+}
+
+// Stop rule.  Let c be the cell of q' = q clamped into the box [lo, hi] (q' = q inside it).  After shells 0 .. r every cell within
+// Chebyshev distance r of c has been read, so a point p not yet seen has, along some axis a with more than one cell, a cell
+// coordinate that differs from c_a by r + 1 or more.  The cell function is non-decreasing, so r whole cells lie between q'_a and
+// p_a, and |p_a - q'_a| >= r h, h = h_safe a lower bound of every such cell's width.  All points lie in the box, the box is convex
+// and q' is the point of it nearest to q, so (p - q').(q - q') <= 0 and |p - q|^2 >= |p - q'|^2 + |q' - q|^2 >= (r h)^2 + |q - q'|^2.
+// The comparison is strict and the bound is shrunk by 2^-16, far more than the few 2^-24 by which the fp32 evaluation of either
+// side can be off: a point not seen has a strictly larger fp32 squared distance than the best one, so it cannot win, not even a tie.
+// r never exceeds the largest grid dimension - 1 (then every cell has been read), so the loop ends whatever the input is.
+__global__ __launch_bounds__(256) void k_nn_query(const float* __restrict__ query, long long Q, long long P, const NnHeader* __restrict__ head,
+                                                  const int* __restrict__ start, const float4* __restrict__ rec, float* __restrict__ dist,
+                                                  int* __restrict__ index) {
+    const NnHeader h = *head;
+    const bool ok = nn_head_ok(h, P) && h.n_finite > 0;
+    const int nx = h.n[0], ny = h.n[1], nz = h.n[2];
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < Q; i += gridDim.x * 256ll) {
+        const float qx = query[3 * i], qy = query[3 * i + 1], qz = query[3 * i + 2];
+        float best = INFINITY;
+        int arg = -1;
+        if (ok && finite3(qx, qy, qz)) {
+            const float cx_ = fminf(fmaxf(qx, h.lo[0]), h.hi[0]), cy_ = fminf(fmaxf(qy, h.lo[1]), h.hi[1]), cz_ = fminf(fmaxf(qz, h.lo[2]), h.hi[2]);
+            const float ox = qx - cx_, oy = qy - cy_, oz = qz - cz_;
+            const float out2 = ox * ox + oy * oy + oz * oz;
+            const int cx = nn_cell1(cx_, h.lo[0], h.inv_h[0], nx), cy = nn_cell1(cy_, h.lo[1], h.inv_h[1], ny), cz = nn_cell1(cz_, h.lo[2], h.inv_h[2], nz);
+            const int rmax = max(max(max(cx, nx - 1 - cx), max(cy, ny - 1 - cy)), max(cz, nz - 1 - cz));
+            for (int r = 0; r <= rmax; ++r) {
+                const int x0 = max(cx - r, 0), x1 = min(cx + r, nx - 1), y0 = max(cy - r, 0), y1 = min(cy + r, ny - 1);
+                const int z0 = max(cz - r, 0), z1 = min(cz + r, nz - 1);
+                for (int x = x0; x <= x1; ++x) {
+                    const bool xface = x == cx - r || x == cx + r;
+                    for (int y = y0; y <= y1; ++y) {
+                        const int col = (x * ny + y) * nz;
+                        if (xface || y == cy - r || y == cy + r) {
+                            nn_scan_run(rec, start, P, col + z0, col + z1, qx, qy, qz, best, arg);
+                        } else {
+                            if (cz - r >= 0) nn_scan_run(rec, start, P, col + cz - r, col + cz - r, qx, qy, qz, best, arg);
+                            if (cz + r < nz && r > 0) nn_scan_run(rec, start, P, col + cz + r, col + cz + r, qx, qy, qz, best, arg);
+                        }
+                    }
+                }
+                const float reach = (float)r * h.h_safe;
+                if (best < (reach * reach + out2) * (1.f - 1.f / 65536.f)) break;
+            }
+        }
+        dist[i] = arg >= 0 ? nn_sqrt_rn(best) : INFINITY;
+        index[i] = arg;
+    }
+}
+
+static int mesh_check(long long V, long long T) {
+    ES_REQUIRE(V >= 0 && T >= 0, "mesh: negative vertex or triangle count");
+    ES_REQUIRE(V < MESH_MAX && T < MESH_MAX, "mesh: 2^31 vertices or triangles or more (indices are int32)");
+    return ST_OK;
+}
+static int nn_check(long long P, long long Q) {
+    ES_REQUIRE(P >= 0 && Q >= 0, "nearest: negative point or query count");
+    ES_REQUIRE(P < MESH_MAX && Q < MESH_MAX, "nearest: 2^31 points or queries or more (indices are int32)");
+    return ST_OK;
+}
+
+}  // namespace es
+
+using namespace es;
+
+#define MESH_SCRATCH_OK(scratch) \
+    ES_REQUIRE(scratch && reinterpret_cast<uintptr_t>(scratch) % 16 == 0, "mesh scratch must be a 16-byte aligned device buffer")
+
+extern "C" {
+
+int64_t es_mesh_scratch_bytes(long long n_verts, long long n_tris) {
+    if (mesh_check(n_verts, n_tris) != ST_OK) return -1;
+    return mesh_scratch_bytes(n_verts, n_tris);
+}
+
+int es_mesh_cc_begin(const int* tris, long long V, long long T, void* scratch, void* stream) {
+    if (const int s = mesh_check(V, T)) return s;
+    ES_REQUIRE(tris || T == 0, "es_mesh_cc_begin needs tris");
+    MESH_SCRATCH_OK(scratch);
+    if (V == 0) return ST_OK;
+    const MeshScratch s = mesh_carve(scratch, V, T);
+    hipLaunchKernelGGL(k_mesh_init, dim3(mesh_grid(V)), dim3(256), 0, static_cast<hipStream_t>(stream), s.parent, (int)V);
+    return hip_last("es_mesh_cc_begin");
+}
+
+int es_mesh_cc_round(const int* tris, long long V, long long T, void* scratch, int* changed, void* stream) {
+    if (const int s = mesh_check(V, T)) return s;
+    ES_REQUIRE((tris || T == 0) && changed, "es_mesh_cc_round needs tris and changed");
+    MESH_SCRATCH_OK(scratch);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ES_HIP(hipMemsetAsync(changed, 0, sizeof(int), st));
+    if (V == 0 || T == 0) return ST_OK;
+    const MeshScratch s = mesh_carve(scratch, V, T);
+    hipLaunchKernelGGL(k_mesh_hook, dim3(mesh_grid(T)), dim3(256), 0, st, tris, (int)V, T, s.parent, changed);
+    for (int pass = 0, n = mesh_jump_passes(V); pass < n; ++pass)
+        hipLaunchKernelGGL(k_mesh_jump, dim3(mesh_grid(V)), dim3(256), 0, st, s.parent, (int)V);
+    return hip_last("es_mesh_cc_round");
+}
+
+int es_mesh_cc_finish(const int* tris, long long V, long long T, const void* scratch, int* vertex_label, int* triangle_label, int* component_triangles,
+                      long long* totals, void* stream) {
+    if (const int s = mesh_check(V, T)) return s;
+    ES_REQUIRE((tris || T == 0) && totals, "es_mesh_cc_finish needs tris and totals");
+    ES_REQUIRE((V == 0 || (vertex_label && component_triangles)) && (T == 0 || triangle_label),
+               "es_mesh_cc_finish needs vertex_label, triangle_label and component_triangles");
+    MESH_SCRATCH_OK(scratch);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const MeshScratch s = mesh_carve(const_cast<void*>(scratch), V, T);
+    ES_HIP(hipMemsetAsync(totals, 0, 3 * sizeof(long long), st));
+    if (V > 0) {
+        ES_HIP(hipMemcpyAsync(vertex_label, s.parent, 4 * V, hipMemcpyDeviceToDevice, st));
+        ES_HIP(hipMemsetAsync(component_triangles, 0, 4 * V, st));
+    }
+    unsigned long long* tot = reinterpret_cast<unsigned long long*>(totals);
+    if (T > 0)
+        hipLaunchKernelGGL(k_mesh_label, dim3(mesh_grid(T)), dim3(256), 0, st, tris, (int)V, T, s.parent, triangle_label, component_triangles, tot);
+    if (V > 0) hipLaunchKernelGGL(k_mesh_stats, dim3(mesh_grid(V)), dim3(256), 0, st, component_triangles, (int)V, tot);
+    return hip_last("es_mesh_cc_finish");
+}
+
+int es_mesh_keep_count(const int* tris, long long V, long long T, const int* triangle_label, const int* component_triangles, double keep_ratio,
+                       long long max_triangles, int compact, void* scratch, long long* totals, void* stream) {
+    if (const int s = mesh_check(V, T)) return s;
+    ES_REQUIRE(keep_ratio >= 0.0 && keep_ratio <= 1.0, "es_mesh_keep_count: keep_ratio must be in [0, 1]");
+    ES_REQUIRE(max_triangles >= 0 && max_triangles <= T, "es_mesh_keep_count: max_triangles outside 0..T");
+    ES_REQUIRE(totals && (T == 0 || (tris && triangle_label && component_triangles)),
+               "es_mesh_keep_count needs tris, triangle_label, component_triangles and totals");
+    MESH_SCRATCH_OK(scratch);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const MeshScratch s = mesh_carve(scratch, V, T);
+    if (V > 0) ES_HIP(hipMemsetAsync(s.vflag, compact ? 0 : 1, V, st));
+    if (T > 0)
+        hipLaunchKernelGGL(k_mesh_keep_flags, dim3(mesh_grid(T)), dim3(256), 0, st, tris, (int)V, T, triangle_label, component_triangles,
+                           keep_ratio * (double)max_triangles, compact, s.tflag, s.vflag);
+    hipLaunchKernelGGL(k_mesh_keep_blocksum, dim3((unsigned)s.nblk), dim3(256), 0, st, s.vflag, V, s.tflag, T, s.bsum);
+    hipLaunchKernelGGL(k_mesh_scan_blocks, dim3(1), dim3(256), 0, st, s.bsum, s.nblk, s.boff, totals);
+    hipLaunchKernelGGL(k_mesh_keep_offsets, dim3((unsigned)s.nblk), dim3(256), 0, st, s.vflag, V, s.tflag, T, s.boff, s.voff, s.toff);
+    return hip_last("es_mesh_keep_count");
+}
+
+int es_mesh_keep_emit(const float* verts, const int* tris, long long V, long long T, const void* scratch, long long V2, long long T2, float* verts_out,
+                      int* tris_out, long long* vertex_map, void* stream) {
+    if (const int s = mesh_check(V, T)) return s;
+    ES_REQUIRE(V2 >= 0 && V2 <= V && T2 >= 0 && T2 <= T, "es_mesh_keep_emit: kept counts outside 0..V / 0..T");
+    MESH_SCRATCH_OK(scratch);
+    if (V2 == 0 && T2 == 0) return ST_OK;
+    ES_REQUIRE((T2 == 0 || (tris && tris_out)) && (!verts_out || verts), "es_mesh_keep_emit needs tris, tris_out and verts for verts_out");
+    const MeshScratch s = mesh_carve(const_cast<void*>(scratch), V, T);
+    hipLaunchKernelGGL(k_mesh_keep_emit, dim3(mesh_grid(V > T ? V : T)), dim3(256), 0, static_cast<hipStream_t>(stream), verts, tris, (int)V, T, s.voff,
+                       s.toff, s.vflag, s.tflag, (int)V2, (int)T2, verts_out, tris_out, vertex_map);
+    return hip_last("es_mesh_keep_emit");
+}
+
+int64_t es_nn_scratch_bytes(long long n_points) {
+    if (nn_check(n_points, 0) != ST_OK) return -1;
+    return nn_scratch_bytes(n_points);
+}
+
+int es_nn_build(const float* points, long long P, void* scratch, void* stream) {
+    if (const int s = nn_check(P, 0)) return s;
+    ES_REQUIRE(points || P == 0, "es_nn_build needs points");
+    MESH_SCRATCH_OK(scratch);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const NnScratch s = nn_carve(scratch, P);
+    const int nparts = (int)(mesh_grid(P) < (unsigned)NN_PARTS ? mesh_grid(P) : (unsigned)NN_PARTS);
+    ES_HIP(hipMemsetAsync(s.count, 0, reinterpret_cast<char*>(s.start) - reinterpret_cast<char*>(s.count), st));          // count and cursor
+    hipLaunchKernelGGL(k_nn_bbox, dim3(nparts), dim3(256), 0, st, points, P, s.part);
+    hipLaunchKernelGGL(k_nn_header, dim3(1), dim3(256), 0, st, s.part, nparts, s.head);
+    if (P == 0) return hip_last("es_nn_build");
+    hipLaunchKernelGGL(k_nn_count, dim3(mesh_grid(P)), dim3(256), 0, st, points, P, s.head, s.cell, s.count);
+    hipLaunchKernelGGL(k_nn_blocksum, dim3((unsigned)s.nblk), dim3(256), 0, st, s.count, P + 1, s.bsum);
+    hipLaunchKernelGGL(k_mesh_scan_blocks, dim3(1), dim3(256), 0, st, s.bsum, s.nblk, s.boff, static_cast<long long*>(nullptr));
+    hipLaunchKernelGGL(k_nn_offsets, dim3((unsigned)s.nblk), dim3(256), 0, st, s.count, P + 1, s.boff, s.start);
+    hipLaunchKernelGGL(k_nn_fill, dim3(mesh_grid(P)), dim3(256), 0, st, points, P, s.cell, s.start, s.cursor, s.rec);
+    return hip_last("es_nn_build");
+}
+
+int es_nn_query(const float* query, long long Q, long long P, const void* scratch, float* dist, int* index, void* stream) {
+    if (const int s = nn_check(P, Q)) return s;
+    if (Q == 0) return ST_OK;
+    ES_REQUIRE(query && dist && index, "es_nn_query needs query, dist and index");
+    MESH_SCRATCH_OK(scratch);
+    const NnScratch s = nn_carve(const_cast<void*>(scratch), P);
+    hipLaunchKernelGGL(k_nn_query, dim3(mesh_grid(Q)), dim3(256), 0, static_cast<hipStream_t>(stream), query, Q, P, s.head, s.start, s.rec, dist, index);
+    return hip_last("es_nn_query");
+}
+
+}  // extern "C"

@@ -149,3 +149,43 @@ def cal_rmse(a, b, mask) -> float:
     if mask.ndim == a.ndim - 1:
         mask = mask[..., None]
     return float((((a - b) ** 2 * mask).sum() / (np.sum(mask) + 1e-10)) ** 0.5)
+
+
+def depth_points(depth, intrinsics, pose, depth_trunc) -> torch.Tensor:
+    """The point cloud of one depth frame (what the reference's gen_pcd makes through Open3D, src/trainer/utils.py:249-277, with
+    ``project_valid_depth_only``): for every pixel with 0 < depth <= depth_trunc, in pixel order,
+    pose[:3,:3] @ (K^-1 [x, y, 1] * depth) + pose[:3,3] with integer pixel coordinates: ``get_rays``' convention, depth being the
+    z-depth of the point in the camera frame.  depth [H,W] (or [H,W,1]), intrinsics and pose [4,4] (camera to world; intrinsics
+    may be [3,3]) -> [M,3] fp32 on ``depth``'s device.  One synchronisation (the number of valid pixels)."""
+    d = torch.as_tensor(depth, dtype=torch.float32)
+    if d.dim() == 3 and d.shape[-1] == 1:
+        d = d[..., 0]
+    if d.dim() != 2:
+        raise ValueError(f"depth must be [H, W] or [H, W, 1] (got {tuple(d.shape)})")
+    dev = d.device
+    k = torch.as_tensor(intrinsics, dtype=torch.float32).to(dev)
+    c2w = torch.as_tensor(pose, dtype=torch.float32).to(dev)
+    h, w = d.shape
+    ys, xs = torch.meshgrid(torch.arange(h, device=dev, dtype=torch.float32), torch.arange(w, device=dev, dtype=torch.float32), indexing="ij")
+    valid = (d > 0) & (d <= float(depth_trunc))
+    pix = torch.stack([xs[valid], ys[valid], torch.ones_like(xs[valid])], -1)                   # [M,3]
+    cam = (pix @ torch.inverse(k[:3, :3]).T) * d[valid][:, None]
+    return cam @ c2w[:3, :3].T + c2w[:3, 3][None]
+
+
+def cal_geometric_error(points, vertices, depth_scale: float = 1.0, engine=None) -> float:
+    """The reference's 3D metric for one frame (trainer_endosurf.py demo: ``pcd_gt.compute_point_cloud_distance(mesh vertices)``
+    averaged, times the depth scale): mean over ``points`` [M,3] (the ground truth, ``depth_points``) of the distance to the nearest
+    row of ``vertices`` [V,3], times ``depth_scale``.  Device tensors go through ``engine.nearest`` (an ``Engine`` of their device is
+    made when none is given), anything else through the numpy twin ``meshing.nearest``.  nan for an empty cloud, inf for no vertices."""
+    if torch.is_tensor(points) and torch.is_tensor(vertices) and points.is_cuda and vertices.is_cuda:
+        if engine is None:
+            from .engine import Engine
+            engine = Engine(points.device)
+        with torch.cuda.device(engine.device):
+            dist, _ = engine.nearest(points, vertices)
+        return float(dist.double().mean()) * float(depth_scale) if dist.numel() else float("nan")
+    from .meshing import nearest
+    as_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    dist, _ = nearest(as_np(points), as_np(vertices))
+    return float(dist.astype(np.float64).mean()) * float(depth_scale) if dist.size else float("nan")

@@ -696,6 +696,97 @@ class Engine:
         verts, tris, ends = self.iso_surface(field, threshold)
         return verts, tris, ends, stats
 
+    # ---- connected components, largest-component filter, nearest neighbour (csrc/mesh.hip) ----------------------------
+    def _mesh_args(self, tris, n_verts, what):
+        """``tris`` as the library reads it (int32 [T, 3], contiguous, on this device) and V, checked: one read-back of the index range."""
+        if tris.dim() != 2 or tris.shape[1] != 3 or tris.device != self.device or tris.dtype not in (torch.int32, torch.int64):
+            raise _lib.EndoSurfHipError(f"{what} takes [T, 3] int32 / int64 triangles on {self.device} (got {tris.dtype} {tuple(tris.shape)} "
+                                        f"on {tris.device})")
+        V, T = int(n_verts), int(tris.shape[0])
+        if V < 0 or V >= 1 << 31 or T >= 1 << 31:
+            raise _lib.EndoSurfHipError(f"{what}: {V} vertices / {T} triangles do not fit int32 indices")
+        if T:
+            lo, hi = (int(v) for v in torch.stack([tris.min(), tris.max()]).tolist())
+            if lo < 0 or hi >= V:
+                raise _lib.EndoSurfHipError(f"{what}: triangle indices {lo}..{hi} outside [0, {V})")
+        return tris.detach().to(torch.int32).contiguous(), V, T
+
+    def _mesh_scratch(self, V, T):
+        nbytes = int(self.lib.es_mesh_scratch_bytes(V, T))
+        if nbytes < 0:
+            check(1, "es_mesh_scratch_bytes")
+        return self.empty(nbytes, dtype=torch.uint8)
+
+    def _mesh_components(self, t32, V, T, scratch):
+        st = self.st()
+        changed = self.empty(1, dtype=torch.int32)
+        totals = self.empty(3, dtype=torch.int64)
+        vlabel, tlabel, counts = (self.empty(n, dtype=torch.int32) for n in (V, T, V))
+        check(self.lib.es_mesh_cc_begin(ptr(t32), V, T, ptr(scratch), st), "es_mesh_cc_begin")
+        rounds = 0
+        while True:          # the fixed point is reached in O(log V) rounds on meshes; V rounds always suffice (each joins two trees)
+            check(self.lib.es_mesh_cc_round(ptr(t32), V, T, ptr(scratch), ptr(changed), st), "es_mesh_cc_round")
+            rounds += 1
+            if not int(changed.item()):
+                break
+            if rounds > V + 1:
+                raise _lib.EndoSurfHipError(f"mesh_components did not reach its fixed point in {rounds} rounds")
+        check(self.lib.es_mesh_cc_finish(ptr(t32), V, T, ptr(scratch), ptr(vlabel), ptr(tlabel), ptr(counts), ptr(totals), st),
+              "es_mesh_cc_finish")
+        ncomp, biggest, degenerate = (int(v) for v in totals.tolist())
+        stats = {"components": ncomp, "max_triangles": biggest, "kept_triangles": T - degenerate, "degenerate": degenerate, "rounds": rounds}
+        return vlabel, tlabel, counts, stats
+
+    def mesh_components(self, tris: torch.Tensor, n_verts: int):
+        """Connected components of a device mesh, by the rule of ``meshing.mesh_components`` (its numpy twin): vertex connectivity,
+        degenerate triangles join nothing, label = the smallest vertex index of the component.  (vertex_label [V], triangle_label [T]
+        (-1 = degenerate), component_triangles [V], stats), int32 device tensors; ``stats``: components (with a triangle),
+        max_triangles, kept_triangles (= the non-degenerate ones here), degenerate, rounds.  The host reads one integer per round."""
+        t32, V, T = self._mesh_args(tris, n_verts, "mesh_components")
+        return self._mesh_components(t32, V, T, self._mesh_scratch(V, T))
+
+    def keep_components(self, verts: torch.Tensor, tris: torch.Tensor, keep_ratio: float = 0.9, compact: bool = True):
+        """The mesh without the triangles of small components (``meshing.keep_components`` is the numpy twin and the specification):
+        a triangle stays iff it is not degenerate and its component has at least ``keep_ratio`` x the triangles of the largest one.
+        (verts [V', 3], tris [T', 3] int32, vertex_map [V'] int64, stats); order is kept, ``vertex_map`` is the old index of each new
+        vertex (``attr.index_select(0, vertex_map)`` moves per-vertex attributes along).  ``compact=False`` drops triangles only."""
+        if verts.dim() != 2 or verts.shape[1] != 3 or verts.device != self.device:
+            raise _lib.EndoSurfHipError(f"keep_components takes [V, 3] vertices on {self.device} (got {tuple(verts.shape)} on {verts.device})")
+        ratio = float(keep_ratio)
+        if not 0.0 <= ratio <= 1.0:
+            raise _lib.EndoSurfHipError(f"keep_components: keep_ratio must be in [0, 1] (got {keep_ratio!r})")
+        v32 = f32(verts)
+        t32, V, T = self._mesh_args(tris, v32.shape[0], "keep_components")
+        scratch, st = self._mesh_scratch(V, T), self.st()
+        _, tlabel, counts, stats = self._mesh_components(t32, V, T, scratch)
+        totals = self.empty(2, dtype=torch.int64)
+        check(self.lib.es_mesh_keep_count(ptr(t32), V, T, ptr(tlabel), ptr(counts), ratio, stats["max_triangles"], int(bool(compact)),
+                                          ptr(scratch), ptr(totals), st), "es_mesh_keep_count")
+        V2, T2 = (int(v) for v in totals.tolist())
+        verts_out, tris_out, vmap = self.empty(V2, 3), self.empty(T2, 3, dtype=torch.int32), self.empty(V2, dtype=torch.int64)
+        check(self.lib.es_mesh_keep_emit(ptr(v32), ptr(t32), V, T, ptr(scratch), V2, T2, ptr(verts_out), ptr(tris_out), ptr(vmap), st),
+              "es_mesh_keep_emit")
+        stats["kept_triangles"] = T2
+        return verts_out, tris_out, vmap, stats
+
+    def nearest(self, query: torch.Tensor, points: torch.Tensor):
+        """Exact nearest neighbour of each ``query`` row among the rows of ``points`` ([Q, 3], [P, 3] on this device): (dist [Q] fp32,
+        index [Q] int32) by the rule of ``meshing.nearest`` (the numpy twin): fp32 squared distance, ties to the smallest index,
+        non-finite rows never an answer, inf / -1 where there is none; bit-identical from call to call.  No read-back."""
+        for name, t in (("query", query), ("points", points)):
+            if t.dim() != 2 or t.shape[1] != 3 or t.device != self.device:
+                raise _lib.EndoSurfHipError(f"nearest takes [N, 3] {name} on {self.device} (got {tuple(t.shape)} on {t.device})")
+        q, p = f32(query), f32(points)
+        Q, P = int(q.shape[0]), int(p.shape[0])
+        nbytes = int(self.lib.es_nn_scratch_bytes(P))
+        if nbytes < 0:
+            check(1, "es_nn_scratch_bytes")
+        scratch, st = self.empty(nbytes, dtype=torch.uint8), self.st()
+        dist, index = self.empty(Q), self.empty(Q, dtype=torch.int32)
+        check(self.lib.es_nn_build(ptr(p), P, ptr(scratch), st), "es_nn_build")
+        check(self.lib.es_nn_query(ptr(q), Q, P, ptr(scratch), ptr(dist), ptr(index), st), "es_nn_query")
+        return dist, index
+
     # ---- per-kernel timers (csrc/timing.hip) ---------------------------------------------------------
     def timing_enable(self, on: bool):
         self._timing_on = bool(on)          # (events cannot be recorded inside a captured graph: the renderer's captured forward stands down)

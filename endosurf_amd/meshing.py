@@ -187,3 +187,113 @@ def band_field(sample, axes, threshold=0.0, block=8, lipschitz=1.0, max_fraction
         r += 1
     stats.update(active_blocks=int((rnd > 0).sum()), rounds=int(rnd.max()) - 1 if rnd.max() > 0 else 0)
     return (field, stats, rnd) if return_blocks else (field, stats)
+
+
+# ---- connected components, the largest-component filter, nearest neighbour (host twins of csrc/mesh.hip; contract: DESIGN.md 7b) -------
+def _as_triangles(triangles, n_vertices):
+    tri = np.asarray(triangles)
+    if tri.size == 0:
+        tri = np.zeros((0, 3), np.int64)
+    if tri.ndim != 2 or tri.shape[1] != 3 or not np.issubdtype(tri.dtype, np.integer):
+        raise ValueError(f"triangles must be an integer [T, 3] array (got {tri.dtype} {tri.shape})")
+    V = int(n_vertices)
+    if V < 0 or V >= 1 << 31 or len(tri) >= 1 << 31:
+        raise ValueError("vertex / triangle counts must be in [0, 2^31)")
+    tri = tri.astype(np.int64)
+    if len(tri) and (tri.min() < 0 or tri.max() >= V):
+        raise ValueError(f"triangle indices outside [0, {V})")
+    return tri, V
+
+
+def mesh_components(triangles, n_vertices):
+    """Connected components of an indexed triangle mesh (numpy twin of ``Engine.mesh_components``).
+
+    A triangle with a repeated index is degenerate: it joins nothing and counts for nothing.  Two other triangles are connected when
+    they share a vertex index (Open3D's ``cluster_connected_triangles`` asks for a shared edge: the two differ only where two sheets
+    touch in a single vertex, which this rule merges).  The label of a component is its smallest vertex index.
+    Returns (vertex_label [V] int32: a vertex of no non-degenerate triangle is its own label, triangle_label [T] int32: -1 for a
+    degenerate triangle, component_triangles [V] int32: the triangle count at the label's index, 0 elsewhere)."""
+    return _components(*_as_triangles(triangles, n_vertices))[:3]
+
+
+def _components(tri, V):
+    """mesh_components of checked arguments, and the number of hooking rounds it took (the last one, which finds nothing, included)."""
+    good = (tri[:, 0] != tri[:, 1]) & (tri[:, 1] != tri[:, 2]) & (tri[:, 0] != tri[:, 2])
+    t = tri[good]
+    parent = np.arange(V, dtype=np.int64)
+    rounds = 0
+    while len(t):          # min-label hooking of the roots, then pointer jumping until flat: O(log V) rounds
+        rounds += 1
+        r = parent[t]
+        m = r.min(axis=1)
+        if (r == m[:, None]).all():
+            break
+        np.minimum.at(parent, r.reshape(-1), np.repeat(m, 3))
+        while True:
+            nxt = parent[parent]
+            if np.array_equal(nxt, parent):
+                break
+            parent = nxt
+    tlabel = np.full(len(tri), -1, np.int64)
+    tlabel[good] = parent[t[:, 0]]
+    counts = np.bincount(tlabel[good], minlength=V)[:V] if V else np.zeros(0, np.int64)
+    return parent.astype(np.int32), tlabel.astype(np.int32), counts.astype(np.int32), rounds
+
+
+def keep_components(vertices, triangles, keep_ratio=0.9, compact=True):
+    """The triangles of the largest components (numpy twin of ``Engine.keep_components``): triangle i stays iff it is not degenerate
+    and NOT ``component_triangles[label_i] < keep_ratio * max(component_triangles)`` (fp64, the comparison of the reference's
+    trainer_endosurf.py:444 with keep_ratio = 0.9).  Kept triangles and vertices keep their input order; duplicate triangles are not
+    removed.  ``compact=True`` drops the vertices no kept triangle uses and renumbers; ``compact=False`` keeps every vertex (what the
+    reference does, which never calls ``remove_unreferenced_vertices``).
+    Returns (vertices [V', 3], triangles [T', 3] int32, vertex_map [V'] int64: the old index of each new vertex, stats)."""
+    verts = np.asarray(vertices)
+    if verts.ndim != 2 or verts.shape[1] != 3:
+        raise ValueError(f"vertices must be [V, 3] (got {verts.shape})")
+    ratio = float(keep_ratio)
+    if not 0.0 <= ratio <= 1.0:
+        raise ValueError("keep_ratio must be in [0, 1]")
+    tri, V = _as_triangles(triangles, len(verts))
+    _, tlabel, counts, rounds = _components(tri, V)
+    biggest = int(counts.max()) if V else 0
+    good = tlabel >= 0
+    keep = good.copy()
+    keep[good] = ~(counts[tlabel[good]] < ratio * biggest)
+    used = np.ones(V, bool)
+    if compact:
+        used = np.zeros(V, bool)
+        used[tri[keep].reshape(-1)] = True
+    vmap = np.nonzero(used)[0].astype(np.int64)
+    new_id = np.cumsum(used) - 1
+    stats = {"components": int((counts > 0).sum()), "max_triangles": biggest, "kept_triangles": int(keep.sum()),
+             "degenerate": int((~good).sum()), "rounds": rounds}
+    return verts[vmap], new_id[tri[keep]].astype(np.int32).reshape(-1, 3), vmap, stats
+
+
+def nearest(query, points, chunk=1 << 22):
+    """Exact nearest neighbour (numpy twin of ``Engine.nearest``, chunked brute force): for each query row the row of ``points`` with
+    the smallest fp32 squared distance (dx dx + dy dy) + dz dz, the smallest index among equal ones; dist = its square root.  Non-finite
+    rows of ``points`` (and points whose squared distance overflows) are never an answer; a query without an answer gets inf and -1.
+    Returns (dist [Q] float32, index [Q] int32)."""
+    q = np.ascontiguousarray(np.asarray(query, np.float32).reshape(-1, 3))
+    p = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+    Q, P = len(q), len(p)
+    if P >= 1 << 31 or Q >= 1 << 31:
+        raise ValueError("point / query counts must be below 2^31")
+    best = np.full(Q, np.inf, np.float32)
+    arg = np.full(Q, -1, np.int64)
+    ids = np.nonzero(np.isfinite(p).all(axis=1))[0]
+    pf = p[ids]
+    rows = max(1, int(chunk) // max(len(pf), 1))
+    with np.errstate(over="ignore", invalid="ignore"):
+        for q0 in range(0, Q if len(pf) else 0, rows):
+            d = q[q0:q0 + rows, None, :] - pf[None, :, :]
+            d *= d
+            d2 = (d[..., 0] + d[..., 1]) + d[..., 2]
+            d2[~np.isfinite(d2)] = np.inf          # (a non-finite query row, an overflow)
+            k = np.argmin(d2, axis=1)               # the first minimum: pf is in index order
+            v = d2[np.arange(len(k)), k]
+            hit = np.isfinite(v)
+            best[q0:q0 + rows] = np.where(hit, v, np.inf)
+            arg[q0:q0 + rows] = np.where(hit, ids[k], -1)
+    return np.sqrt(best), arg.astype(np.int32)

@@ -709,6 +709,20 @@ class EndoSurfRenderer(nn.Module):
         bmax = torch.as_tensor(bound_max, dtype=torch.float32).to(self.device).reshape(1, 3)
         return verts / (resolution - 1.0) * (bmax - bmin) + bmin, tris
 
+    @staticmethod
+    def _components_arg(components):
+        """The ``components`` keyword as Engine.keep_components' arguments, or None: 0.9 / True (= 0.9) / dict(keep_ratio, compact)."""
+        if components is None or components is False:
+            return None
+        if components is True:
+            return dict(keep_ratio=0.9, compact=True)
+        if isinstance(components, dict):
+            unknown = set(components) - {"keep_ratio", "compact"}
+            if unknown:
+                raise TypeError(f"components takes keep_ratio and compact (got {sorted(unknown)})")
+            return dict(keep_ratio=float(components.get("keep_ratio", 0.9)), compact=bool(components.get("compact", True)))
+        return dict(keep_ratio=float(components), compact=True)
+
     def _mesh_on_device_band(self, t, bound_min, bound_max, resolution, threshold, net_chunk, band):
         """``_mesh_on_device`` from a field sampled near the surface only, plus the counts of ``Engine.band_field``.  ``band``: True or
         a dict of block / lipschitz / max_fraction."""
@@ -744,22 +758,29 @@ class EndoSurfRenderer(nn.Module):
 
     @_on_device
     def extract_observation_geometry(self, t, bound_min, bound_max, resolution, threshold=0.0, net_chunk=1 << 22, cpu=True, on_device=False,
-                                     band=None):
+                                     band=None, components=None):
         """(vertices, triangles) of the observed-space surface at time t (reference endosurf.py:490-500 + extract_geometry,
         utils.py:128-136).  Field sampling runs on the GPU.  By default the field is copied to the host and the iso-surface extractor
         is PyMCubes when installed (as in the reference), otherwise endosurf_amd.meshing.marching_tetrahedra (different triangulation
         of the same level set).  ``on_device=True`` extracts on the GPU as well (``Engine.iso_surface``: marching_tetrahedra's
         triangulation, fp32 vertices, int32 triangles) and returns numpy arrays when ``cpu`` else device tensors.  With ``on_device``,
         ``band=True`` or ``band=dict(block=8, lipschitz=1.0, max_fraction=0.5)`` queries the SDF near the surface only (see
-        ``extract_observation_mesh``); the default ``None`` samples every grid point."""
+        ``extract_observation_mesh``); the default ``None`` samples every grid point.  With ``on_device``, ``components=0.9`` (or True,
+        or dict(keep_ratio=0.9, compact=True)) keeps the largest connected components only (``Engine.keep_components``; see
+        ``extract_observation_mesh``); the default ``None`` keeps every triangle."""
         use_band = band is not None and band is not False
+        comp = self._components_arg(components)
         if use_band and not on_device:
             raise ValueError("band needs on_device=True (the narrow-band field is assembled on the GPU)")
-        if use_band:
-            vertices, triangles, _ = self._mesh_on_device_band(t, bound_min, bound_max, resolution, threshold, net_chunk, band)
-            return (vertices.cpu().numpy(), triangles.cpu().numpy()) if cpu else (vertices, triangles)
+        if comp is not None and not on_device:
+            raise ValueError("components needs on_device=True (the component filter runs on the GPU)")
         if on_device:
-            vertices, triangles = self._mesh_on_device(t, bound_min, bound_max, resolution, threshold, net_chunk)
+            if use_band:
+                vertices, triangles, _ = self._mesh_on_device_band(t, bound_min, bound_max, resolution, threshold, net_chunk, band)
+            else:
+                vertices, triangles = self._mesh_on_device(t, bound_min, bound_max, resolution, threshold, net_chunk)
+            if comp is not None:
+                vertices, triangles, _, _ = self.engine.keep_components(vertices, triangles, **comp)
             return (vertices.cpu().numpy(), triangles.cpu().numpy()) if cpu else (vertices, triangles)
         from .meshing import iso_surface
         u = self.extract_fields(bound_min, bound_max, resolution, t, net_chunk)
@@ -771,7 +792,7 @@ class EndoSurfRenderer(nn.Module):
 
     @_on_device
     def extract_observation_mesh(self, t, bound_min, bound_max, resolution, threshold=0.0, net_chunk=1 << 22, view_point=None, refine_steps=0,
-                                 band=None):
+                                 band=None, components=None):
         """The observed-space surface at time t as a coloured mesh, device tensors only (what the reference's demo assembles from
         extract_observation_geometry + renderonpts, trainer_endosurf.py:403-460): ``vertices`` [V,3] world coordinates, ``triangles``
         [T,3] int32, ``normals`` [V,3] the analytic observed-space SDF gradient at the vertices normalised as renderonpts does, ``sdf``
@@ -790,11 +811,23 @@ class EndoSurfRenderer(nn.Module):
         bit-identical, in the dense vertex and triangle order: the whole mesh when |grad sdf| <= lipschitz holds in the culled blocks.
         What a too small ``lipschitz`` can lose is a closed floater smaller than a block that no block corner sees.  Bit-identity is
         stated for the default fp32 query; with ``engine.split_precision`` the band follows ``query_sdf``'s choice of kernel per launch.
-        The default ``None`` is the dense path."""
+        The default ``None`` is the dense path.
+
+        ``components=0.9``, ``True`` (= 0.9) or ``dict(keep_ratio=0.9, compact=True)`` removes, right after the iso-surface and before
+        refinement, normals and colours (so the point evaluations run on the kept vertices only), every triangle whose connected
+        component has fewer than ``keep_ratio`` x the triangles of the largest one -- the reference demo's floater filter
+        (trainer_endosurf.py:440-445), by ``Engine.keep_components`` (csrc/mesh.hip): components by shared vertices, degenerate
+        triangles dropped, order kept; ``compact=False`` keeps the orphaned vertices as the reference does.  Adds ``components`` (a dict
+        of counts: components, max_triangles, kept_triangles, degenerate, rounds) to the result.  The filter removes exactly what a
+        too small band ``lipschitz`` can lose, so band and dense agree behind it.  The default ``None`` keeps every triangle."""
+        comp = self._components_arg(components)
         if band is not None and band is not False:
             vertices, triangles, stats = self._mesh_on_device_band(t, bound_min, bound_max, resolution, threshold, net_chunk, band)
         else:
             (vertices, triangles), stats = self._mesh_on_device(t, bound_min, bound_max, resolution, threshold, net_chunk), None
+        cstats = None
+        if comp is not None:
+            vertices, triangles, _, cstats = self.engine.keep_components(vertices, triangles, **comp)
         tt = torch.as_tensor(t, dtype=torch.float32, device=self.device).reshape(-1)[:1]
         chunk = max(1, min(int(net_chunk), 1 << 17))
 
@@ -806,6 +839,8 @@ class EndoSurfRenderer(nn.Module):
         out = {"vertices": vertices, "triangles": triangles}
         if stats is not None:
             out["stats"] = stats
+        if cstats is not None:
+            out["components"] = cstats
         if vertices.shape[0] == 0:
             out.update(normals=vertices.clone(), sdf=vertices.new_zeros(0))
             if view_point is not None:
@@ -830,6 +865,18 @@ class EndoSurfRenderer(nn.Module):
             s, _ = sdf_grad(vertices)
         out["sdf"] = s.reshape(-1)
         return out
+
+    @_on_device
+    def geometric_error(self, mesh_or_vertices, depth, intrinsics, pose, depth_trunc, depth_scale=1.0) -> float:
+        """The reference demo's 3D number for one frame (trainer_endosurf.py:418 / geo_errs): the ground-truth depth frame
+        back-projected into a point cloud (``data.depth_points``: depth [H,W] z-depths, intrinsics, camera-to-world pose, pixels with
+        0 < depth <= depth_trunc), and the mean distance from its points to the nearest mesh vertex times ``depth_scale``
+        (``Engine.nearest``: exact, on the device).  ``mesh_or_vertices``: the dict of ``extract_observation_mesh`` or [V,3] vertices."""
+        from .data import cal_geometric_error, depth_points
+        verts = mesh_or_vertices["vertices"] if isinstance(mesh_or_vertices, dict) else mesh_or_vertices
+        verts = torch.as_tensor(verts, dtype=torch.float32).to(self.device)
+        pts = depth_points(torch.as_tensor(depth, dtype=torch.float32).to(self.device), intrinsics, pose, depth_trunc)
+        return cal_geometric_error(pts, verts, depth_scale, engine=self.engine)
 
     @_on_device
     def sdf_observed(self, pts, t):
