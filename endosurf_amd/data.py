@@ -151,6 +151,13 @@ def cal_rmse(a, b, mask) -> float:
     return float((((a - b) ** 2 * mask).sum() / (np.sum(mask) + 1e-10)) ** 0.5)
 
 
+def to8b(img):
+    """An image in [0, 1] as the uint8 the reference writes its panels with (src/trainer/utils.py to8b: 255 clip(x, 0, 1), truncated);
+    a numpy array, ready for any PNG writer."""
+    x = img.detach().cpu().numpy() if torch.is_tensor(img) else np.asarray(img)
+    return (255 * np.clip(x, 0, 1)).astype(np.uint8)
+
+
 def depth_points(depth, intrinsics, pose, depth_trunc) -> torch.Tensor:
     """The point cloud of one depth frame (what the reference's gen_pcd makes through Open3D, src/trainer/utils.py:249-277, with
     ``project_valid_depth_only``): for every pixel with 0 < depth <= depth_trunc, in pixel order,

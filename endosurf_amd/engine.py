@@ -787,6 +787,83 @@ class Engine:
         check(self.lib.es_nn_query(ptr(q), Q, P, ptr(scratch), ptr(dist), ptr(index), st), "es_nn_query")
         return dist, index
 
+    # ---- mesh rasteriser (csrc/raster.hip) ------------------------------------------------------------------------------
+    def project_vertices(self, vertices: torch.Tensor, intrinsics, pose):
+        """Stage A of the rasteriser (``meshing.project_vertices`` is the numpy twin and the specification): world vertices [V, 3]
+        through the pinhole camera ``intrinsics`` ([3,3] or [4,4]) at the camera-to-world ``pose`` [4,4] of ``data.get_rays``, in fp64:
+        (xy [V, 2] int32 in 1/256-pixel fixed point, zc [V] fp32 camera depth, NaN for a non-finite vertex), on the device."""
+        from .meshing import camera_params
+        if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.device != self.device:
+            raise _lib.EndoSurfHipError(f"project_vertices takes [V, 3] vertices on {self.device} (got {tuple(vertices.shape)} on {vertices.device})")
+        cam = (C.c_double * 17)(*camera_params(intrinsics, pose).tolist())
+        v32 = f32(vertices)
+        V = int(v32.shape[0])
+        xy, zc = self.empty(V, 2, dtype=torch.int32), self.empty(V)
+        check(self.lib.es_rast_project(ptr(v32), V, cam, ptr(xy), ptr(zc), self.st()), "es_rast_project")
+        return xy, zc
+
+    def rasterize_projected(self, xy: torch.Tensor, zc: torch.Tensor, triangles: torch.Tensor, height: int, width: int, attributes=None,
+                            near: float = 1e-6, cull: str = "none"):
+        """Stage B of the rasteriser on the output of ``project_vertices`` (``meshing.rasterize_projected`` is the numpy twin and the
+        specification): the dict of ``rasterize``.  The host reads the number of work items back between counting and filling, and
+        the counts of ``stats`` at the end."""
+        from .meshing import RAST_CULL, RAST_MAX_ATTRS, RAST_MAX_SIZE, RAST_REASONS
+        H, W = int(height), int(width)
+        if not (1 <= H <= RAST_MAX_SIZE and 1 <= W <= RAST_MAX_SIZE):
+            raise _lib.EndoSurfHipError(f"rasterize: height and width must be in 1..{RAST_MAX_SIZE} (got {height!r}, {width!r})")
+        if cull not in RAST_CULL:
+            raise _lib.EndoSurfHipError(f"rasterize: cull must be one of {sorted(RAST_CULL)} (got {cull!r})")
+        if xy.dim() != 2 or xy.shape[1] != 2 or xy.dtype != torch.int32 or zc.dim() != 1 or zc.shape[0] != xy.shape[0] \
+                or xy.device != self.device or zc.device != self.device:
+            raise _lib.EndoSurfHipError(f"rasterize takes xy [V, 2] int32 and zc [V] on {self.device}")
+        if triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.device != self.device or triangles.dtype not in (torch.int32, torch.int64):
+            raise _lib.EndoSurfHipError(f"rasterize takes [T, 3] int32 / int64 triangles on {self.device} (got {triangles.dtype} "
+                                        f"{tuple(triangles.shape)} on {triangles.device})")
+        V, T = int(zc.shape[0]), int(triangles.shape[0])
+        att, Cn = None, 0
+        if attributes is not None:
+            if attributes.dim() != 2 or attributes.shape[0] != V or not 1 <= attributes.shape[1] <= RAST_MAX_ATTRS or attributes.device != self.device:
+                raise _lib.EndoSurfHipError(f"rasterize takes [V, 1..{RAST_MAX_ATTRS}] attributes on {self.device} (got {tuple(attributes.shape)})")
+            att, Cn = f32(attributes), int(attributes.shape[1])
+        out = {"depth": None, "triangle": None, "bary": None, "attributes": None,
+               "stats": dict({name: 0 for name in RAST_REASONS}, triangles=T, work_items=0, covered_pixels=0)}
+        if V == 0 or T == 0:          # nothing to draw: no launch
+            out.update(depth=torch.full((H, W), float("inf"), device=self.device), triangle=torch.full((H, W), -1, dtype=torch.int32, device=self.device),
+                       bary=torch.zeros(H, W, 3, device=self.device), attributes=torch.zeros(H, W, Cn, device=self.device))
+            out["stats"]["invalid"] = T
+            return out
+        xy32, zc32, t32 = xy.contiguous(), f32(zc), triangles.detach().to(torch.int32).contiguous()
+        nbytes = int(self.lib.es_rast_scratch_bytes(V, T, H, W))
+        if nbytes < 0:
+            check(1, "es_rast_scratch_bytes")
+        scratch, totals, st = self.empty(nbytes, dtype=torch.uint8), self.empty(8, dtype=torch.int64), self.st()
+        view = (H, W, float(near), RAST_CULL[cull], ptr(scratch))
+        check(self.lib.es_rast_count(ptr(t32), V, T, ptr(xy32), ptr(zc32), *view, ptr(totals), st), "es_rast_count")
+        n_work = int(totals[0].item())
+        check(self.lib.es_rast_fill(ptr(t32), V, T, ptr(xy32), ptr(zc32), *view, n_work, st), "es_rast_fill")
+        depth, tri, bary = self.empty(H, W), self.empty(H, W, dtype=torch.int32), self.empty(H, W, 3)
+        attr = self.empty(H, W, Cn)
+        check(self.lib.es_rast_resolve(ptr(t32), V, T, ptr(xy32), ptr(zc32), ptr(att), Cn, *view[:4], ptr(scratch), ptr(depth), ptr(tri), ptr(bary),
+                                       ptr(attr) if Cn else None, ptr(totals), st), "es_rast_resolve")
+        tt = totals.tolist()
+        out["stats"].update({name: int(tt[1 + i]) for i, name in enumerate(RAST_REASONS)}, work_items=int(tt[0]), covered_pixels=int(tt[6]))
+        out.update(depth=depth, triangle=tri, bary=bary, attributes=attr)
+        return out
+
+    def rasterize(self, vertices: torch.Tensor, triangles: torch.Tensor, intrinsics, pose, height: int, width: int, attributes=None,
+                  near: float = 1e-6, cull: str = "none"):
+        """A device mesh as images of a pinhole camera, without a display: ``depth`` [H, W] fp32 (camera z, the convention of
+        ``data.depth_points``; +inf where nothing is hit), ``triangle`` [H, W] int32 (-1), ``bary`` [H, W, 3] (perspective-correct
+        weights of the triangle's corners; 0), ``attributes`` [H, W, C] (the per-vertex ``attributes`` [V, C <= 8] interpolated with
+        them; 0) and ``stats`` (triangles, rejected ones by reason -- invalid, near_rejected, zero_area, culled, offscreen --,
+        work_items, covered_pixels).  Pixel (row i, column j) is sampled where ``data.get_rays`` casts its ray; one sample per pixel.
+        A triangle with a corner not farther than ``near`` along the camera axis is dropped whole (no clipping); ``cull`` = "none",
+        "back" or "front" (the front is the side the normal (v1 - v0) x (v2 - v0) points to: the outside of ``iso_surface``'s meshes).
+        ``meshing.rasterize`` is the numpy twin; the rules of coverage and depth are in ``meshing.rasterize_projected``.  Equal depths
+        go to the smaller triangle index, so the images are bit-identical from call to call."""
+        xy, zc = self.project_vertices(vertices, intrinsics, pose)
+        return self.rasterize_projected(xy, zc, triangles, height, width, attributes, near, cull)
+
     # ---- per-kernel timers (csrc/timing.hip) ---------------------------------------------------------
     def timing_enable(self, on: bool):
         self._timing_on = bool(on)          # (events cannot be recorded inside a captured graph: the renderer's captured forward stands down)

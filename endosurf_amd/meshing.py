@@ -297,3 +297,213 @@ def nearest(query, points, chunk=1 << 22):
             best[q0:q0 + rows] = np.where(hit, v, np.inf)
             arg[q0:q0 + rows] = np.where(hit, ids[k], -1)
     return np.sqrt(best), arg.astype(np.int32)
+
+
+# ---- mesh rasteriser (host twins of csrc/raster.hip; contract: DESIGN.md 7c) ---------------------------------------------------------
+RAST_SUBPIXEL = 256                  # fixed-point units per pixel
+RAST_GUARD = 1 << 22                 # |fixed-point coordinate| <= this: every edge function fits in int64 with room to spare
+RAST_MAX_SIZE = 8192                 # largest image side
+RAST_MAX_ATTRS = 8
+RAST_CULL = {"none": 0, "back": 1, "front": 2}
+RAST_REASONS = ("invalid", "near_rejected", "zero_area", "culled", "offscreen")          # count[t] = -1 .. -4, and 0 tiles
+
+
+def camera_params(intrinsics, pose):
+    """The 17 fp64 numbers both rasterisers read: R [9] (row-major rotation of the camera-to-world ``pose``), t [3], K00, K01, K02,
+    K11, K12 of the upper-triangular ``intrinsics`` ([3,3] or [4,4]).  Raises for non-finite entries, K00 or K11 not positive, a last
+    intrinsics row other than (0, 0, 1), or a pose whose rotation is not orthonormal with determinant +1 (to 1e-3)."""
+    K = np.asarray(intrinsics.detach().cpu() if hasattr(intrinsics, "detach") else intrinsics, np.float64)
+    P = np.asarray(pose.detach().cpu() if hasattr(pose, "detach") else pose, np.float64)
+    if K.shape not in ((3, 3), (4, 4)) or P.shape != (4, 4):
+        raise ValueError(f"intrinsics must be [3,3] or [4,4] and pose [4,4] (got {K.shape}, {P.shape})")
+    cam = np.concatenate([P[:3, :3].reshape(-1), P[:3, 3], [K[0, 0], K[0, 1], K[0, 2], K[1, 1], K[1, 2]]])
+    if not np.isfinite(cam).all():
+        raise ValueError("camera parameters must be finite")
+    if not (K[0, 0] > 0 and K[1, 1] > 0) or K[1, 0] != 0 or tuple(K[2, :3]) != (0.0, 0.0, 1.0):
+        raise ValueError("intrinsics must be upper triangular with positive focal lengths and a last row (0, 0, 1)")
+    R = P[:3, :3]
+    if np.abs(R.T @ R - np.eye(3)).max() > 1e-3 or np.linalg.det(R) < 0:
+        raise ValueError("pose must be rigid (camera to world: an orthonormal rotation of determinant +1 and a translation)")
+    return cam
+
+
+def project_vertices(vertices, intrinsics, pose):
+    """Stage A of the rasteriser (numpy twin of ``Engine.project_vertices``): world vertices [V,3] through the pinhole camera of
+    ``data.get_rays`` -- x_cam = R^T (x - t), u = (K00 x + K01 y) / z + K02, v = K11 y / z + K12 in fp64, pixel (row i, column j)
+    being the image point (u, v) = (j, i).  Returns (xy [V,2] int32 = rint(256 u), rint(256 v) clamped to +-2^22 (NaN -> 0),
+    zc [V] float32 = the camera z, NaN for a vertex with a non-finite coordinate)."""
+    cam = camera_params(intrinsics, pose)
+    x = np.asarray(vertices, np.float32).reshape(-1, 3).astype(np.float64)
+    R, t = cam[:9].reshape(3, 3), cam[9:12]
+    with np.errstate(all="ignore"):
+        d = x - t[None]
+        c = [(R[0, i] * d[:, 0] + R[1, i] * d[:, 1]) + R[2, i] * d[:, 2] for i in range(3)]
+        u = (cam[12] * c[0] + cam[13] * c[1]) / c[2] + cam[14]
+        v = cam[15] * c[1] / c[2] + cam[16]
+        q = np.stack([u, v], -1) * float(RAST_SUBPIXEL)
+        q = np.where(np.isnan(q), 0.0, np.clip(q, -float(RAST_GUARD), float(RAST_GUARD)))
+        ok = np.isfinite(x).all(axis=1) & np.isfinite(c[2])
+        zc = np.where(ok, c[2], np.nan).astype(np.float32)
+    return np.rint(q).astype(np.int32), zc
+
+
+def _rast_setup(xy, zc, tri, H, W, near, cull):
+    """Per triangle: reason (0 = drawn, 1 + index into RAST_REASONS otherwise), pixel box [T,4] = jmin, jmax, imin, imax, and the
+    number of 8 x 8 tiles the box touches."""
+    V, T = len(zc), len(tri)
+    reason = np.zeros(T, np.int64)
+    a, b, c = tri[:, 0], tri[:, 1], tri[:, 2]
+    bad = (tri < 0).any(1) | (tri >= V).any(1) | (a == b) | (b == c) | (a == c)
+    s = np.where(bad[:, None], 0, tri)
+    if V == 0:          # (every triangle is invalid: one row to index)
+        xy, zc = np.zeros((1, 2), np.int32), np.zeros(1, np.float32)
+    p = xy[s].astype(np.int64)                                                  # [T,3,2]
+    z = zc[s].astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        behind = ~(z > near).all(1)
+    area = (p[:, 1, 0] - p[:, 0, 0]) * (p[:, 2, 1] - p[:, 0, 1]) - (p[:, 1, 1] - p[:, 0, 1]) * (p[:, 2, 0] - p[:, 0, 0])
+    culled = ((cull == 1) & (area > 0)) | ((cull == 2) & (area < 0))          # the front of a triangle has a NEGATIVE screen area (y down)
+    S = RAST_SUBPIXEL
+    jmin = np.clip(-((-p[..., 0].min(1)) // S), 0, None)
+    jmax = np.clip(p[..., 0].max(1) // S, None, W - 1)
+    imin = np.clip(-((-p[..., 1].min(1)) // S), 0, None)
+    imax = np.clip(p[..., 1].max(1) // S, None, H - 1)
+    off = (jmin > jmax) | (imin > imax)
+    for code, m in ((5, off), (4, culled), (3, area == 0), (2, behind), (1, bad)):          # the first test that fires names the reason
+        reason[m] = code
+    tiles = np.where(reason == 0, ((jmax >> 3) - (jmin >> 3) + 1) * ((imax >> 3) - (imin >> 3) + 1), 0)
+    return reason, np.stack([jmin, jmax, imin, imax], 1), tiles, p, z, area
+
+
+def rasterize_projected(xy, zc, triangles, height, width, attributes=None, near=1e-6, cull="none", runner_up=False, chunk=1 << 22):
+    """Stage B of the rasteriser, the specification of csrc/raster.hip: a pure function of the snapped vertices.
+
+    A triangle is rejected when an index repeats or lies outside [0, V) (``invalid``), a corner has ``zc`` not > ``near`` (no clipping:
+    the whole triangle goes, ``near_rejected``), its doubled fixed-point area A = (p1 - p0) x (p2 - p0) is 0 (``zero_area``), or by
+    ``cull`` (``culled``: "back" drops A > 0, "front" A < 0 -- with the image's y axis pointing down, the side the normal
+    (v1 - v0) x (v2 - v0) points to is seen with A < 0); ``offscreen`` counts drawn triangles whose box holds no pixel centre.
+    Coverage of the pixel centre P = (256 j, 256 i): with s = sign(A) and, for the edge from a to b opposite corner k,
+    E_k = (bx - ax)(Py - ay) - (by - ay)(Px - ax), the pixel is covered iff for every k  s E_k > 0, or E_k == 0 and the edge d = s (b - a)
+    is a left edge (dy < 0) or a top edge (dy == 0, dx > 0).  That is the sign of s E_k at P + (eps, eps^2): a centre on a shared edge,
+    or on a vertex of a closed fan, belongs to exactly one triangle.
+    Depth (fp64 from the exact integers, no multiply feeds an add): l_k = E_k / A, w_k = l_k / zc_k, z = 1 / ((w_0 + w_1) + w_2),
+    b_k = w_k z.  The visible triangle has the smallest (bits of float32(z), index) pair.
+
+    Returns a dict: ``depth`` [H,W] float32 (+inf: nothing), ``triangle`` [H,W] int32 (-1), ``bary`` [H,W,3] float32 (0),
+    ``attributes`` [H,W,C] float32 = (b_0 a_0 + b_1 a_1) + b_2 a_2 in fp32 (0; C = 0 without attributes), ``stats``; with ``runner_up``
+    also ``second_depth`` [H,W] float32 (+inf), the depth of the second smallest pair."""
+    H, W = int(height), int(width)
+    if not (1 <= H <= RAST_MAX_SIZE and 1 <= W <= RAST_MAX_SIZE):
+        raise ValueError(f"height and width must be in 1..{RAST_MAX_SIZE}")
+    if cull not in RAST_CULL:
+        raise ValueError(f"cull must be one of {sorted(RAST_CULL)}")
+    near = float(near)
+    if not (near >= 0.0 and np.isfinite(near)):
+        raise ValueError("near must be finite and >= 0")
+    xy = np.asarray(xy, np.int32).reshape(-1, 2)
+    zc = np.asarray(zc, np.float32).reshape(-1)
+    tri = np.asarray(triangles)
+    tri = (np.zeros((0, 3), np.int64) if tri.size == 0 else tri.astype(np.int64)).reshape(-1, 3)
+    V, T = len(zc), len(tri)
+    if len(xy) != V or V >= 1 << 31 or T >= 1 << 31:
+        raise ValueError("xy [V,2] and zc [V] must agree, and V, T must be below 2^31")
+    att = None
+    if attributes is not None:
+        att = np.asarray(attributes, np.float32)
+        if att.ndim != 2 or att.shape[0] != V or not 1 <= att.shape[1] <= RAST_MAX_ATTRS:
+            raise ValueError(f"attributes must be [V, 1..{RAST_MAX_ATTRS}]")
+    C = 0 if att is None else att.shape[1]
+    reason, box, tiles, p, z, area = _rast_setup(xy, zc, tri, H, W, near, RAST_CULL[cull])
+    stats = {name: int((reason == i + 1).sum()) for i, name in enumerate(RAST_REASONS)}
+    stats.update(triangles=T, work_items=int(tiles.sum()))
+    if stats["work_items"] >= 1 << 31:
+        raise ValueError("2^31 work items or more")
+    EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
+    ids = np.nonzero(reason == 0)[0]
+    nj, ni = box[ids, 1] - box[ids, 0] + 1, box[ids, 3] - box[ids, 2] + 1
+    cand = nj * ni
+    pix_all, key_all = [np.zeros(0, np.int64)], [np.zeros(0, np.uint64)]
+    start = 0
+    while start < len(ids):          # runs of triangles with at most ``chunk`` box pixels together
+        csum = np.cumsum(cand[start:])
+        stop = start + max(1, int(np.searchsorted(csum, chunk, side="right")))
+        sel, n = ids[start:stop], cand[start:stop]
+        which = np.repeat(np.arange(len(sel)), n)
+        local = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+        t = sel[which]
+        j = box[t, 0] + local % nj[start:stop][which]
+        i = box[t, 2] + local // nj[start:stop][which]
+        Px, Py = j * RAST_SUBPIXEL, i * RAST_SUBPIXEL
+        q, s = p[t], np.sign(area[t])
+        E, inside = [], np.ones(len(t), bool)
+        for k in range(3):
+            a, b = q[:, (k + 1) % 3], q[:, (k + 2) % 3]
+            dx, dy = b[:, 0] - a[:, 0], b[:, 1] - a[:, 1]
+            e = dx * (Py - a[:, 1]) - dy * (Px - a[:, 0])
+            E.append(e)
+            owns = (s * dy < 0) | ((dy == 0) & (s * dx > 0))
+            inside &= (s * e > 0) | ((e == 0) & owns)
+        t, i, j = t[inside], i[inside], j[inside]
+        A = area[t].astype(np.float64)
+        w = [(E[k][inside].astype(np.float64) / A) / z[t, k] for k in range(3)]
+        depth = (1.0 / ((w[0] + w[1]) + w[2])).astype(np.float32)
+        key_all.append((depth.view(np.uint32).astype(np.uint64) << np.uint64(32)) | t.astype(np.uint64))
+        pix_all.append(i * W + j)
+        start = stop
+    pix, key = np.concatenate(pix_all), np.concatenate(key_all)
+    order = np.lexsort((key, pix))
+    pix, key = pix[order], key[order]
+    first = np.ones(len(pix), bool)
+    first[1:] = pix[1:] != pix[:-1]
+    zbuf = np.full(H * W, EMPTY, np.uint64)
+    zbuf[pix[first]] = key[first]
+    hit = zbuf != EMPTY
+    tid = np.where(hit, zbuf & np.uint64(0xFFFFFFFF), 0).astype(np.int64)
+    out_depth = np.where(hit, (zbuf >> np.uint64(32)).astype(np.uint32).view(np.float32), np.float32(np.inf)).astype(np.float32)
+    bary = np.zeros((H * W, 3), np.float32)
+    attr = np.zeros((H * W, C), np.float32)
+    hp = np.nonzero(hit)[0]
+    if len(hp):          # the winner's weights again, as the resolve kernel recomputes them
+        t = tid[hp]
+        Px, Py = (hp % W) * RAST_SUBPIXEL, (hp // W) * RAST_SUBPIXEL
+        q, A = p[t], area[t].astype(np.float64)
+        w = []
+        for k in range(3):
+            a, b = q[:, (k + 1) % 3], q[:, (k + 2) % 3]
+            e = (b[:, 0] - a[:, 0]) * (Py - a[:, 1]) - (b[:, 1] - a[:, 1]) * (Px - a[:, 0])
+            w.append((e.astype(np.float64) / A) / z[t, k])
+        zz = 1.0 / ((w[0] + w[1]) + w[2])
+        b32 = np.stack([w[k] * zz for k in range(3)], -1).astype(np.float32)
+        bary[hp] = b32
+        if C:
+            a3 = att[tri[t]]                                                     # [n,3,C]
+            attr[hp] = (b32[:, 0:1] * a3[:, 0] + b32[:, 1:2] * a3[:, 1]) + b32[:, 2:3] * a3[:, 2]
+    stats["covered_pixels"] = int(hit.sum())
+    out = {"depth": out_depth.reshape(H, W), "triangle": np.where(hit, tid, -1).astype(np.int32).reshape(H, W), "bary": bary.reshape(H, W, 3),
+           "attributes": attr.reshape(H, W, C), "stats": stats}
+    if runner_up:
+        second = np.zeros(len(pix), bool)
+        second[1:] = first[:-1] & ~first[1:]
+        sd = np.full(H * W, np.inf, np.float32)
+        sd[pix[second]] = (key[second] >> np.uint64(32)).astype(np.uint32).view(np.float32)
+        out["second_depth"] = sd.reshape(H, W)
+    return out
+
+
+def rasterize(vertices, triangles, intrinsics, pose, height, width, attributes=None, near=1e-6, cull="none", runner_up=False):
+    """A triangle mesh as depth / triangle-id / barycentric / interpolated-attribute images of a pinhole camera (numpy twin of
+    ``Engine.rasterize``): ``project_vertices`` then ``rasterize_projected``, whose docstrings are the contract.  One sample per pixel,
+    at the point ``data.get_rays`` casts the pixel's ray through; depth is the camera z (``data.depth_points``' convention)."""
+    xy, zc = project_vertices(vertices, intrinsics, pose)
+    return rasterize_projected(xy, zc, triangles, height, width, attributes, near, cull, runner_up)
+
+
+def vertex_normals(vertices, triangles):
+    """Area-weighted vertex normals of an indexed mesh (unit length; 0 for a vertex of no triangle with an area)."""
+    v = np.asarray(vertices, np.float64).reshape(-1, 3)
+    f = np.asarray(triangles, np.int64).reshape(-1, 3)
+    n = np.zeros_like(v)
+    fn = np.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
+    for k in range(3):
+        np.add.at(n, f[:, k], fn)
+    return (n / np.maximum(np.linalg.norm(n, axis=1, keepdims=True), 1e-30)).astype(np.float32)

@@ -878,6 +878,88 @@ class EndoSurfRenderer(nn.Module):
         pts = depth_points(torch.as_tensor(depth, dtype=torch.float32).to(self.device), intrinsics, pose, depth_trunc)
         return cal_geometric_error(pts, verts, depth_scale, engine=self.engine)
 
+    def _mesh_arg(self, mesh):
+        """(vertices [V,3] fp32, triangles [T,3], the dict or None) of a mesh given as ``extract_observation_mesh``'s dict or as
+        (vertices, triangles), on the renderer's device."""
+        d = mesh if isinstance(mesh, dict) else None
+        v, f = (mesh["vertices"], mesh["triangles"]) if d is not None else mesh
+        v = torch.as_tensor(v, dtype=torch.float32).to(self.device)
+        f = torch.as_tensor(f).to(self.device)
+        return v, (f if f.dtype in (torch.int32, torch.int64) else f.to(torch.int64)), d
+
+    @_on_device
+    def render_mesh(self, mesh, intrinsics, pose, height, width, view_point=None, cull="none"):
+        """The three pictures the reference's demo takes of an extracted mesh (vis_mesh through Open3D's Visualizer, the
+        "Mesh / Texture / Normal" panels), from the pinhole camera ``intrinsics`` / camera-to-world ``pose`` of ``data.get_rays``,
+        without a display: ``Engine.rasterize`` (csrc/raster.hip) once, shaded three times.  ``mesh``: the dict of
+        ``extract_observation_mesh`` or (vertices, triangles).  Returns float images in [0, 1], [H,W,3], background 1.0:
+        ``color`` (the vertex colours interpolated and clipped; grey 0.7 for a mesh without ``colors``), ``normal`` ((-n 0.5 + 0.5).clip(0, 1) of the
+        interpolated, re-normalised vertex normals: the demo's paint), ``geometry`` (grey head-light shading |n . v|, v the unit direction
+        from the surface point to the camera); and ``depth`` [H,W] (camera z, +inf on the background), ``mask`` [H,W] bool,
+        ``triangle`` [H,W] int32, ``stats``.  Normals are the mesh's ``normals`` when present, else area-weighted triangle normals.
+        ``view_point`` [3] replaces the camera position as the eye of the head light."""
+        from .meshing import camera_params
+        v, f, d = self._mesh_arg(mesh)
+        H, W = int(height), int(width)
+        cam = camera_params(intrinsics, pose)
+        normals = d.get("normals") if d is not None else None
+        if normals is None:
+            f64 = f.long()
+            fn = torch.linalg.cross(v[f64[:, 1]] - v[f64[:, 0]], v[f64[:, 2]] - v[f64[:, 0]]) if f.shape[0] else v.new_zeros(0, 3)
+            normals = torch.zeros_like(v)
+            for k in range(3):
+                normals.index_add_(0, f64[:, k], fn)
+            normals = normals / torch.linalg.norm(normals, dim=-1, keepdim=True).clamp_min(1e-30)
+        colors = d.get("colors") if d is not None else None
+        if colors is None:
+            colors = torch.full_like(v, 0.7)
+        attrs = torch.cat([f32(colors).to(self.device), f32(normals).to(self.device)], -1)
+        ras = self.engine.rasterize(v, f, intrinsics, pose, H, W, attributes=attrs, cull=cull)
+        hit = ras["triangle"] >= 0
+        m3 = hit[..., None]
+        one = torch.ones(H, W, 3, device=self.device)
+        n = ras["attributes"][..., 3:6]
+        n = n / torch.linalg.norm(n, dim=-1, keepdim=True).clamp_min(1e-30)
+        # the surface point of a pixel: its ray K^-1 [j, i, 1] at the camera depth, rotated to the world
+        R = torch.tensor(cam[:9].reshape(3, 3), dtype=torch.float32, device=self.device)
+        tr = torch.tensor(cam[9:12], dtype=torch.float32, device=self.device)
+        k00, k01, k02, k11, k12 = (float(c) for c in cam[12:17])
+        ii, jj = torch.meshgrid(torch.arange(H, device=self.device, dtype=torch.float32), torch.arange(W, device=self.device, dtype=torch.float32),
+                                indexing="ij")
+        yc = (ii - k12) / k11
+        xc = (jj - k02 - k01 * yc) / k00
+        z = torch.where(hit, ras["depth"], torch.zeros_like(ras["depth"]))
+        pw = (torch.stack([xc, yc, torch.ones_like(xc)], -1) * z[..., None]) @ R.T + tr
+        eye = tr if view_point is None else torch.as_tensor(view_point, dtype=torch.float32).to(self.device).reshape(3)
+        to_eye = eye - pw
+        to_eye = to_eye / torch.linalg.norm(to_eye, dim=-1, keepdim=True).clamp_min(1e-30)
+        shade = (n * to_eye).sum(-1, keepdim=True).abs().clamp(0.0, 1.0).expand(H, W, 3)
+        return {"color": torch.where(m3, ras["attributes"][..., 0:3].clamp(0.0, 1.0), one),
+                "normal": torch.where(m3, (-n * 0.5 + 0.5).clamp(0.0, 1.0), one),
+                "geometry": torch.where(m3, shade, one),
+                "depth": ras["depth"], "mask": hit, "triangle": ras["triangle"], "stats": ras["stats"]}
+
+    @_on_device
+    def mesh_depth_error(self, mesh, depth, mask, intrinsics, pose, depth_scale=1.0):
+        """The 2D counterpart of ``geometric_error``: the mesh rasterised from the camera ``intrinsics`` / ``pose`` of a depth frame
+        (``Engine.rasterize``: camera z per pixel), against that frame.  ``depth`` [H,W] (or [H,W,1]) z-depths, ``mask`` likewise (non-zero =
+        the pixel counts).  Returns dict(``rmse`` = ``data.cal_rmse`` over the masked pixels the mesh covers, times ``depth_scale`` (nan
+        when there is none), ``coverage`` = the fraction of masked pixels the mesh covers)."""
+        from .data import cal_rmse
+        v, f, _ = self._mesh_arg(mesh)
+        d = torch.as_tensor(depth, dtype=torch.float32).to(self.device)
+        m = torch.as_tensor(mask).to(self.device)
+        d = d[..., 0] if d.dim() == 3 and d.shape[-1] == 1 else d
+        m = (m[..., 0] if m.dim() == 3 and m.shape[-1] == 1 else m) != 0
+        if d.dim() != 2 or m.shape != d.shape:
+            raise ValueError(f"depth and mask must be [H, W] or [H, W, 1] (got {tuple(d.shape)}, {tuple(m.shape)})")
+        ras = self.engine.rasterize(v, f, intrinsics, pose, d.shape[0], d.shape[1])
+        both = m & (ras["triangle"] >= 0)
+        n_mask, n_both = int(m.sum()), int(both.sum())
+        mesh_depth = torch.where(both, ras["depth"], torch.zeros_like(d))
+        rmse = cal_rmse(mesh_depth, torch.where(both, d, torch.zeros_like(d)), both.to(torch.float32)) * float(depth_scale) if n_both else float("nan")
+        return {"rmse": rmse, "coverage": n_both / n_mask if n_mask else float("nan")}
+
     @_on_device
     def sdf_observed(self, pts, t):
         """get_sdf_from_observed_space (endosurf.py:570-579) for [M,3] points and [M] / scalar time, no grad."""
