@@ -151,11 +151,77 @@ def cal_rmse(a, b, mask) -> float:
     return float((((a - b) ** 2 * mask).sum() / (np.sum(mask) + 1e-10)) ** 0.5)
 
 
+def _on_gpu(*tensors) -> bool:
+    return all(torch.is_tensor(t) and t.is_cuda for t in tensors if t is not None)
+
+
+def _engine_for(t, engine):
+    if engine is None:
+        from .engine import Engine
+        engine = Engine(t.device)
+    return engine
+
+
+def cal_ssim(a, b, mask, device=None, engine=None) -> float:
+    """src/trainer/utils.py:444-457 (and the SSIM class above it): the mean structural similarity of two stacks [n,H,W,C] times
+    ``mask`` ([n,H,W,1] or [n,H,W]; None = ones), with L = 1.  Device tensors go through ``Engine.ssim`` (csrc/metrics.hip; an
+    ``Engine`` of their device is made when none is given), anything else through the numpy twin ``imaging.ssim``; ``device`` is
+    accepted for the reference's signature and ignored.  Contract and the one divergence (L is not guessed from the image): DESIGN 7d."""
+    if _on_gpu(a, b, mask):
+        engine = _engine_for(a, engine)
+        with torch.cuda.device(engine.device):
+            return float(engine.ssim(a, b, mask)["mean"])
+    from .imaging import ssim
+    as_np = lambda x: None if x is None else (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x))
+    return ssim(as_np(a), as_np(b), as_np(mask))[0]
+
+
+def cal_psnr_device(a, b, mask, engine=None) -> float:
+    """``cal_psnr`` of fp32 device stacks [n,H,W,C] without copying them to the host: fp64 sums on the device
+    (``Engine.masked_sq_sums``), two numbers read back."""
+    from .imaging import psnr_from_sums
+    engine = _engine_for(a, engine)
+    with torch.cuda.device(engine.device):
+        q = engine.masked_sq_sums(a, b, mask)
+        return psnr_from_sums(float(q["S_total"]), float(q["M_total"]))
+
+
+def cal_rmse_device(a, b, mask, engine=None) -> float:
+    """``cal_rmse`` of fp32 device stacks, as ``cal_psnr_device``."""
+    from .imaging import rmse_from_sums
+    engine = _engine_for(a, engine)
+    with torch.cuda.device(engine.device):
+        q = engine.masked_sq_sums(a, b, mask)
+        return rmse_from_sums(float(q["S_total"]), float(q["M_total"]))
+
+
 def to8b(img):
     """An image in [0, 1] as the uint8 the reference writes its panels with (src/trainer/utils.py to8b: 255 clip(x, 0, 1), truncated);
-    a numpy array, ready for any PNG writer."""
+    a numpy array, ready for ``write_png``."""
     x = img.detach().cpu().numpy() if torch.is_tensor(img) else np.asarray(img)
     return (255 * np.clip(x, 0, 1)).astype(np.uint8)
+
+
+def write_png(path, array) -> None:
+    """An 8-bit image as a PNG file with nothing but the standard library: ``array`` uint8 [H,W] / [H,W,1] (grey) or [H,W,3] (RGB), a
+    numpy array or a tensor (a device tensor is copied to the host).  One IDAT chunk, every row with filter type 0, no interlace."""
+    import struct
+    import zlib
+    x = array.detach().cpu().numpy() if torch.is_tensor(array) else np.asarray(array)
+    if x.ndim == 3 and x.shape[-1] == 1:
+        x = x[..., 0]
+    if x.dtype != np.uint8 or x.ndim not in (2, 3) or (x.ndim == 3 and x.shape[-1] != 3) or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"write_png takes a non-empty uint8 [H, W], [H, W, 1] or [H, W, 3] image (got {x.dtype} {x.shape})")
+    h, w = x.shape[:2]
+    rows = np.ascontiguousarray(x).reshape(h, -1)
+    raw = np.concatenate([np.zeros((h, 1), np.uint8), rows], axis=1).tobytes()          # filter byte 0 in front of every row
+
+    def chunk(kind: bytes, body: bytes) -> bytes:
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
+
+    ihdr = struct.pack(">IIBBBBB", w, h, 8, 2 if x.ndim == 3 else 0, 0, 0, 0)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", ihdr) + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
 
 
 def depth_points(depth, intrinsics, pose, depth_trunc) -> torch.Tensor:

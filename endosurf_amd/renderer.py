@@ -625,6 +625,57 @@ class EndoSurfRenderer(nn.Module):
                 out["color"][i:i + m], out["depth"][i:i + m], out["normal"][i:i + m] = c[:m], d[:m], nm[:m]
         return out
 
+    # ---- frame evaluation (the reference's eval(), trainer_endosurf.py:205-283) ---------------------------------------------------
+    @_on_device
+    def evaluate_rendered(self, rendered, color, depth, mask, color_mask, poses, depth_max, depth_scale=1.0):
+        """``evaluate_frames`` without the rendering: ``rendered`` is the dict of ``render_frames`` (color, depth, normal of n H W
+        rays), the rest as there."""
+        from .imaging import psnr_from_sums, rmse_from_sums
+        eng = self.engine
+        gt = eng._eval_stack("color", color, channels=3)
+        n, H, W, _ = (int(v) for v in gt.shape)
+        col, dep, nrm = rendered["color"].view(n, H, W, 3), rendered["depth"].view(n, H, W, 1), rendered["normal"].view(n, H, W, 3)
+        dgt = eng._eval_stack("depth", depth, channels=1)
+        # one fp64 buffer for every number: SSIM [n + 1] | colour S, M [2n + 2] | depth S, M [2n + 2]; one copy to the host at the end
+        buf = eng.empty(5 * n + 5, dtype=torch.float64)
+        ss = eng.ssim(gt, col, color_mask, out=buf[:n + 1])
+        qc = eng.masked_sq_sums(gt, col, color_mask, out=buf[n + 1:3 * n + 3])
+        qd = eng.masked_sq_sums(dgt, dep, mask, out=buf[3 * n + 3:])
+        pan = eng.eval_panels(gt, col, dgt, dep, nrm, poses, depth_max)
+        ds = abs(float(depth_scale))
+        per_frame = {"psnr": 20.0 * torch.log10(1.0 / torch.sqrt(qc["S"] / ((qc["M"] + 1e-10) * 3.0))), "ssim": ss["per_frame"],
+                     "rmse": torch.sqrt(qd["S"] / (qd["M"] + 1e-10)) * ds}
+        host = buf.cpu().numpy()
+        stats = {"psnr_rgb_vr": psnr_from_sums(host[3 * n + 1], host[3 * n + 2]) if n else float("nan"),
+                 "ssim_rgb_vr": float(host[n]),
+                 "rmse_d_vr": rmse_from_sums(host[5 * n + 3], host[5 * n + 4]) * ds if n else float("nan")}
+        return {"stats": stats, "per_frame": per_frame, "color": col, "depth": dep, "normal": pan["normal"], "normal_world": nrm,
+                "panels": pan["panels"], "sheet": pan["sheet"]}
+
+    @_on_device
+    def evaluate_frames(self, rays, color, depth, mask, color_mask, poses, depth_max, depth_scale=1.0, iter_step=0, ray_chunk=2048,
+                        perturb_overwrite=None):
+        """The reference's ``eval()`` for a set of frames, without moving an image to the host: ``render_frames`` of ``rays``
+        [n,H,W,9], then csrc/metrics.hip on the result (contract: DESIGN.md 7d; twins: ``imaging``).  ``color`` [n,H,W,3], ``depth``,
+        ``mask``, ``color_mask`` [n,H,W,1] (or [n,H,W]) are the ground truth as fp32 device tensors (``FrameSet.get_frame_data_by_index``),
+        ``poses`` [n,4,4] camera to world, ``depth_max`` the scale of the depth panels (the data set's far bound; None: each stack's
+        maximum).  Returns
+          ``stats``      {"psnr_rgb_vr", "ssim_rgb_vr", "rmse_d_vr"}: Python floats under the reference's keys (PSNR and SSIM of the colour
+                         under ``color_mask``, RMSE of depth x ``depth_scale`` under ``mask``; no "lpips_rgb_vr": LPIPS needs network weights
+                         this package does not carry), read back in one small copy;
+          ``per_frame``  {"psnr", "ssim", "rmse"}: device fp64 [n], each frame's own value;
+          ``color``, ``depth``, ``normal_world``   the images of ``render_frames``, [n,H,W,3|1|3]; ``normal`` = ``gen_normal``'s float
+                         result (unit normals in each camera's frame);
+          ``panels``     {rgb_gt, rgb_pred, depth_gt, depth_pred, normal_pred}: uint8 [n,H,W,3] (views of the sheet's columns);
+          ``sheet``      uint8 [n,H,5W,3]: the five side by side in the reference's order, without its text labels.
+        The rgb_gt panel is painted by ``gen_rgb``'s rule like rgb_pred (the reference passes the ground truth through ``to8b``)."""
+        if rays.dim() != 4 or rays.shape[-1] != 9:
+            raise _lib.EndoSurfHipError(f"evaluate_frames takes rays [n, H, W, 9] (got {tuple(rays.shape)})")
+        if tuple(color.shape[:3]) != tuple(rays.shape[:3]):
+            raise _lib.EndoSurfHipError(f"color {tuple(color.shape)} does not belong to rays {tuple(rays.shape)}")
+        rendered = self.render_frames(rays, iter_step=iter_step, ray_chunk=ray_chunk, perturb_overwrite=perturb_overwrite)
+        return self.evaluate_rendered(rendered, color, depth, mask, color_mask, poses, depth_max, depth_scale)
+
     # ---- offline helpers (reference endosurf.py:450-521) -----------------------------------------------------------------
     def _points_color(self, x, t, dirs):
         """(rgb [M,3], g_o [M,3]) at explicit points, no grad: one deform/SDF/colour chain launch (EndoSurfNet.forward

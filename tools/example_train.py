@@ -107,22 +107,23 @@ def main():
     for name in ("geometry", "color", "normal"):
         np.save(os.path.join(args.out, f"mesh_{name}.npy"), to8b(pics[name]))
     np.save(os.path.join(args.out, "mesh_depth.npy"), pics["depth"].cpu().numpy())
-    try:          # PNG files only where a writer is installed already
-        from PIL import Image
-        for name in ("geometry", "color", "normal"):
-            Image.fromarray(to8b(pics[name])).save(os.path.join(args.out, f"mesh_{name}.png"))
-        wrote = "npy + png"
-    except ImportError:
-        try:
-            import imageio
-            for name in ("geometry", "color", "normal"):
-                imageio.imwrite(os.path.join(args.out, f"mesh_{name}.png"), to8b(pics[name]))
-            wrote = "npy + png"
-        except ImportError:
-            wrote = "npy"
+    from endosurf_amd.data import write_png
+    for name in ("geometry", "color", "normal"):
+        write_png(os.path.join(args.out, f"mesh_{name}.png"), to8b(pics[name]))
+    wrote = "npy + png"
     de = renderer2.mesh_depth_error(clean, depth, depth > 0, K, pose)
     print(f"mesh panels 640x512 ({wrote}) in {1e3 * (time.perf_counter() - t1):.1f} ms: {pics['stats']['covered_pixels']} pixels covered by "
           f"{pics['stats']['work_items']} work items; mesh depth against the scene's depth frame: rmse {de['rmse']:.4f}, coverage {de['coverage']:.3f}")
+    # the reference's eval() of that frame, on the device: PSNR / SSIM / depth RMSE against the synthetic scene's own picture of the sphere
+    # (a flat grey ball: the numbers say how far the toy training got, not more) and the five-panel sheet as a file
+    hit = (depth > 0).float()[None, ..., None].to(dev)
+    gt_color = (0.5 * hit).expand(1, 512, 640, 3).contiguous()
+    gt_depth = depth[None, ..., None].to(dev).contiguous()
+    t1 = time.perf_counter()
+    ev = renderer2.evaluate_frames(frame_rays.reshape(1, 512, 640, 9), gt_color, gt_depth, hit, hit, pose[None], depth_max=3.0, iter_step=args.iters,
+                                   perturb_overwrite=False)
+    write_png(os.path.join(args.out, "eval_000.png"), ev["sheet"][0])
+    print(f"eval sheet 3200x512 (eval_000.png) in {time.perf_counter() - t1:.2f} s with the render: " + ", ".join(f"{k} {x:.4f}" for k, x in ev["stats"].items()))
     assert np.isfinite(psnr) and len(v) > 0 and m["vertices"].shape[0] > 0
 
 
