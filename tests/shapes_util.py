@@ -1,5 +1,7 @@
 """Test points for the comparisons with the fp64 oracle away from the golden shapes (test_gpu_backward_shapes.py,
 test_gpu_forward_shapes.py): drawn like test_point_backward's, then screened so that no point sits on a ReLU kink."""
+import contextlib
+
 import numpy as np
 import torch
 
@@ -70,3 +72,23 @@ def inputs(M, seed, use_deform=True, screen=None, mode="trained", count=None):
         count[0] = redrawn
     ws, wg, wc = (torch.from_numpy(rng.normal(size=s).astype(np.float32)) for s in ((M, 1), (M, 3), (M, 3)))
     return x, d, t, ws, wg, wc
+
+
+@contextlib.contextmanager
+def split_chain(eng, split=True, infer_min=1):
+    """The opt-in split-precision family for the calls inside: ``eng.split_precision = True`` and (unless ``infer_min`` is None: the
+    shipped threshold stays) ``eng.x3_infer_min = infer_min``, both restored on the way out.  ``split=False`` changes nothing."""
+    old = (eng.split_precision, eng.x3_infer_min)
+    if split:
+        eng.split_precision = True
+        if infer_min is not None:
+            eng.x3_infer_min = infer_min
+    try:
+        yield
+    finally:
+        eng.split_precision, eng.x3_infer_min = old
+
+
+def routes_split(eng, M, save):
+    """The routing condition of Engine.point_forward (fp32_only aside) on the engine's current settings."""
+    return bool(eng.split_precision and M >= eng.x3_infer_min and (eng.x3_train_chain or not save))

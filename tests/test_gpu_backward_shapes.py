@@ -19,7 +19,7 @@ import weightgen
 from gpu_util import renderer_for
 from oracle import endosurf_oracle as O
 from oracle_util import RENDER_CFG
-from shapes_util import SEED, inputs as _inputs
+from shapes_util import SEED, inputs as _inputs, split_chain
 from test_gpu_backward import FLOOR, POINT_TOL, _dump, _grad_table
 
 pytestmark = pytest.mark.gpu
@@ -68,9 +68,15 @@ def _oracle_point_grads(key, use_deform, x, d, t, ws, wg, wc, n_color):
     return float(ref.detach()), params
 
 
-def _hip_point_grads(r, x, d, t, ws, wg, wc, color, m_color=0, poison=None):
+def _hip_point_grads(r, x, d, t, ws, wg, wc, color, m_color=0, poison=None, split=False):
     """Engine.point_forward / point_backward / weightnorm_backward (through the renderer's packing node, so that the parameters' .grad
-    are filled) on all rows of (x, d, t).  Returns (loss, pad rows of the x_c adjoint [Mp - M, 3])."""
+    are filled) on all rows of (x, d, t).  Returns (loss, pad rows of the x_c adjoint [Mp - M, 3]).  ``split``: forward and backward on
+    the split-precision training chain (shapes_util.split_chain, restored behind the call); the context must say that it ran."""
+    with split_chain(r.engine, split):
+        return _hip_point_grads_on(r, x, d, t, ws, wg, wc, color, m_color, poison, split)
+
+
+def _hip_point_grads_on(r, x, d, t, ws, wg, wc, color, m_color, poison, split):
     from endosurf_amd import _lib
     eng, M = r.engine, x.shape[0]
     for p in r.parameters():
@@ -89,6 +95,7 @@ def _hip_point_grads(r, x, d, t, ws, wg, wc, color, m_color=0, poison=None):
     finally:
         if poison is not None:
             del eng.empty
+    assert not split or (ctx.x3_chain and ctx.px3 is not None), "the split-precision training chain did not run"
     n_color = (m_color if m_color > 0 else M) if color else 0
     f = lambda a: a.double().cpu()
     loss = (f(ctx.view("sdf")) * ws.double()).sum() + (f(ctx.view("go")) * wg.double()).sum()
@@ -126,16 +133,17 @@ def _check_point(r, params, loss, ref, pad, name=None):
 DENSE = [(M, True) for M in (1, 63, 64, 65, 127, 129, 777)] + [(M, False) for M in (1, 65, 129)]
 
 
-def _dense(use_deform, M, color, deterministic=False, poison=None, r=None):
+def _dense(use_deform, M, color, deterministic=False, poison=None, r=None, split=False):
     r = r or _renderer(use_deform)
     r.engine.deterministic = deterministic
     try:
         x, d, t, ws, wg, wc = _inputs(M, 1000 + M, use_deform)
-        loss, pad = _hip_point_grads(r, x, d, t, ws, wg, wc, color, poison=poison)
+        loss, pad = _hip_point_grads(r, x, d, t, ws, wg, wc, color, poison=poison, split=split)
     finally:
         r.engine.deterministic = False
     ref, params = _oracle_point_grads(("dense", use_deform, M, color), use_deform, x, d, t, ws, wg, wc, M if color else 0)
-    return _check_point(r, params, loss, ref, pad, name=f"dense_{int(use_deform)}_{M}_{int(color)}" + ("_det" if deterministic else ""))
+    return _check_point(r, params, loss, ref, pad,
+                        name="x3_" * split + f"dense_{int(use_deform)}_{M}_{int(color)}" + ("_det" if deterministic else ""))
 
 
 @pytest.mark.parametrize("use_deform", [True, False])
@@ -166,17 +174,21 @@ def test_point_backward_workspace_history(poison):
 # ------------------------------------------------------------------------------------------------------------------------------
 # B. colour-less tail, dense; sparse seeds at the launch sizes the oracle cannot be given
 # ------------------------------------------------------------------------------------------------------------------------------
+def _tail_dense(use_deform, tail, split=False):
+    mc, M = 256, 256 + tail
+    r = _renderer(use_deform)
+    x, d, t, ws, wg, wc = _inputs(M, 3000 + M, use_deform)
+    loss, pad = _hip_point_grads(r, x, d, t, ws, wg, wc, True, m_color=mc, split=split)
+    ref, params = _oracle_point_grads(("tail", use_deform, M), use_deform, x, d, t, ws, wg, wc, mc)
+    _check_point(r, params, loss, ref, pad, name=f"x3_tail_{int(use_deform)}_{M}" if split else None)
+
+
 @pytest.mark.parametrize("use_deform", [True, False])
 @pytest.mark.parametrize("tail", [64, 192])
 def test_point_backward_tail_dense(use_deform, tail):
     """m_color = 256 < M = 256 + 64 / 256 + 192: the tail's launch arrangements of point_backward_chains (4 and 12 half-height
     deformation tiles; without a deformation network the tail's SDF tiles at the head of the colour launch), oracle on all rows."""
-    mc, M = 256, 256 + tail
-    r = _renderer(use_deform)
-    x, d, t, ws, wg, wc = _inputs(M, 3000 + M, use_deform)
-    loss, pad = _hip_point_grads(r, x, d, t, ws, wg, wc, True, m_color=mc)
-    ref, params = _oracle_point_grads(("tail", use_deform, M), use_deform, x, d, t, ws, wg, wc, mc)
-    _check_point(r, params, loss, ref, pad)
+    _tail_dense(use_deform, tail)
 
 
 def _sparse_rows(M, m_color, seed, main_every):
@@ -203,12 +215,7 @@ SPARSE = {           # M, m_color, use_deform, every n-th tile of the coloured p
 }
 
 
-@pytest.mark.parametrize("name,deterministic", [("ragged_20031", False), ("train_68608_deform", False), ("train_68608_nodeform", False),
-                                                ("train_68608_deform", True)])
-def test_point_backward_sparse_seeds(name, deterministic):
-    """The parameter gradient is a sum over points of (adjoint seed x per-point term): with seeds that are exactly zero outside a row
-    set K the full-size gradient equals the oracle's gradient on the |K| seeded points, while every tile, weight-gradient task and
-    pad row of the big launch runs on real activations.  68 608 = the fused training launch of config 2 (bench.py's flagship)."""
+def _sparse_seeds(name, deterministic, split=False):
     M, m_color, use_deform, every = SPARSE[name]
     r = _renderer(use_deform)
     K = _sparse_rows(M, m_color, 7, every)
@@ -221,7 +228,7 @@ def test_point_backward_sparse_seeds(name, deterministic):
     ws, wg, wc = ws * keep, wg * keep, wc * keep          # exact zeros off K
     r.engine.deterministic = deterministic
     try:
-        loss, pad = _hip_point_grads(r, x, d, t, ws, wg, wc, True, m_color=m_color)
+        loss, pad = _hip_point_grads(r, x, d, t, ws, wg, wc, True, m_color=m_color, split=split)
     finally:
         r.engine.deterministic = False
     Kc = int((K < n_color).sum())          # K is sorted: its coloured rows come first
@@ -230,7 +237,16 @@ def test_point_backward_sparse_seeds(name, deterministic):
     # gate: POINT_TOL unchanged -- rows with zero seeds add exact zeros to every fp32 sum, so the accumulation floor is that of |K| rows
     # (measured on MI355X, worst tensor / median: 8.3e-6 / 2.1e-6 at 20 031 rows, 5.6e-6 / 2.3e-6 at 68 608 rows with the deformation
     # network, 5.3e-6 / 2.3e-6 in deterministic mode, 2.4e-6 / 7.9e-7 without it; the dense M = 200 case measures up to 2.3e-5)
-    _check_point(r, params, loss, ref, pad, name=name + ("_det" if deterministic else ""))
+    _check_point(r, params, loss, ref, pad, name="x3_" * split + name + ("_det" if deterministic else ""))
+
+
+@pytest.mark.parametrize("name,deterministic", [("ragged_20031", False), ("train_68608_deform", False), ("train_68608_nodeform", False),
+                                                ("train_68608_deform", True)])
+def test_point_backward_sparse_seeds(name, deterministic):
+    """The parameter gradient is a sum over points of (adjoint seed x per-point term): with seeds that are exactly zero outside a row
+    set K the full-size gradient equals the oracle's gradient on the |K| seeded points, while every tile, weight-gradient task and
+    pad row of the big launch runs on real activations.  68 608 = the fused training launch of config 2 (bench.py's flagship)."""
+    _sparse_seeds(name, deterministic)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -22,18 +22,20 @@ import torch
 import weightgen
 from oracle import endosurf_oracle as O
 from oracle_util import RENDER_CFG
-from shapes_util import FORWARD_GATE, RELU_MARGIN, SEED, inputs, oracle_net, relu_margin
+from shapes_util import FORWARD_GATE, RELU_MARGIN, SEED, inputs, oracle_net, relu_margin, routes_split, split_chain
 from test_gpu_backward import LOG
 
 pytestmark = pytest.mark.gpu
-_REPORT, _ENGINES, _ORACLE = {}, {}, {}
+_REPORT, _REPORT_X3, _ENGINES, _ORACLE = {}, {}, {}, {}
 
 
 def _note(case, **values):
-    _REPORT.setdefault(case, {}).update(values)
+    """Cases of the split-precision family (test_gpu_forward_shapes_x3.py; their names start with X3_) go to forward_shapes_x3.json."""
+    report, name = (_REPORT_X3, "forward_shapes_x3.json") if case.startswith("X3_") else (_REPORT, "forward_shapes.json")
+    report.setdefault(case, {}).update(values)
     os.makedirs(LOG, exist_ok=True)
-    with open(os.path.join(LOG, "forward_shapes.json"), "w") as f:
-        json.dump(_REPORT, f, indent=1, sort_keys=True)
+    with open(os.path.join(LOG, name), "w") as f:
+        json.dump(report, f, indent=1, sort_keys=True)
 
 
 def _setup(mode="trained", use_deform=True):
@@ -113,20 +115,29 @@ def _finite(ctx, names, M):
         assert bool(torch.isfinite(v).all()), (k, "non-finite values in rows [0, M)", (~torch.isfinite(v).reshape(M, -1).all(1)).nonzero().flatten()[:8])
 
 
-def _names(use_deform, color):
-    return ["xc", "sdf", "gc", "go"] + (["v", "tbar"] if use_deform else []) + (["feat", "rgb"] if color else [])
+def _names(use_deform, color, split=False):
+    """(the split-precision VJP sweep does not compute the time adjoint: no tbar there)"""
+    return ["xc", "sdf", "gc", "go"] + (["v"] + ([] if split else ["tbar"]) if use_deform else []) + (["feat", "rgb"] if color else [])
 
 
-def _launch(eng, weff, packed, pts, flags, m_color=0, poison=None):
+def _launch(eng, weff, packed, pts, flags, m_color=0, poison=None, split=False, infer_min=1):
+    """``split``: the launch goes through the split-precision family (shapes_util.split_chain, restored behind the call), and did:
+    Engine.point_forward's routing condition holds on the arguments, the context carries the split weights, and with ES_PF_SAVE it is
+    marked as the split training chain's."""
+    from endosurf_amd import _lib
     if poison is not None:          # the workspace starts from ``poison`` in every word instead of whatever torch.empty returns
         plain = eng.empty
         eng.empty = lambda *s, **k: plain(*s, **k).fill_(poison)
     try:
-        ctx = eng.point_forward(pts, weff, packed, flags, m_color)
+        with split_chain(eng, split, infer_min):
+            routed = routes_split(eng, pts.M, bool(flags & _lib.PF_SAVE))
+            ctx = eng.point_forward(pts, weff, packed, flags, m_color)
     finally:
         if poison is not None:
             del eng.empty
     torch.cuda.synchronize()
+    if split:
+        assert routed and ctx.px3 is not None and ctx.x3_chain == bool(flags & _lib.PF_SAVE), (routed, ctx.x3_chain)
     return ctx
 
 
@@ -139,15 +150,16 @@ def _screened(key, M, seed, use_deform, screen=None, mode="trained"):
     return _ORACLE[key]
 
 
-def _dense(mode, use_deform, M, color, save=True, poison=None):
+def _dense(mode, use_deform, M, color, save=True, poison=None, split=False):
     eng, weff, packed, net = _setup(mode, use_deform)
     x, d, t, redrawn = _screened(("dense_in", mode, use_deform, M), M, 7000 + M, use_deform, mode=mode)
     dev = lambda a: a.cuda().contiguous()
-    ctx = _launch(eng, weff, packed, eng.points(x=dev(x), t=dev(t), dirs=dev(d)), _flags(use_deform, color, save), poison=poison)
+    ctx = _launch(eng, weff, packed, eng.points(x=dev(x), t=dev(t), dirs=dev(d)), _flags(use_deform, color, save), poison=poison, split=split)
     ref, own32 = _reference(("dense", mode, use_deform, M), net, x, d, t, True)          # (without colour: the same buffers but feat / rgb)
     case = f"A_dense_{mode}_{int(use_deform)}_{M}_{int(color)}" + ("" if save else "_nosave") + ("" if poison is None else "_poison")
+    case = "X3_" * split + case
     _note(case, redrawn=redrawn)
-    _compare(case, ctx, ref, own32, np.arange(M), names=_names(use_deform, color))
+    _compare(case, ctx, ref, own32, np.arange(M), names=_names(use_deform, color, split))
     return ctx
 
 
@@ -208,19 +220,19 @@ def _large_inputs(name):
     return M, m_color, use_deform, K, x, d, t, redrawn
 
 
-def _compare_large(case, name, ctx, net, K, x, d, t, m_color, use_deform, redrawn):
+def _compare_large(case, name, ctx, net, K, x, d, t, m_color, use_deform, redrawn, split=False, tail_names=None):
     """Rows K of a launch with a colour-less tail behind ``m_color`` coloured rows: the coloured rows against the oracle with colour,
-    the tail rows against the oracle without."""
+    the tail rows against the oracle without (``tail_names``: their buffers, default those of the coloured rows but feat / rgb)."""
     M = x.shape[0]
     n_color = m_color if 0 < m_color < M else M
     Kc, Kt = K[K < n_color], K[K >= n_color]
     _note(case, redrawn=redrawn)
     ref, own32 = _reference(("large", name, "colour"), net, x[Kc], d[Kc], t[Kc], True)
-    _compare(case + "_colour", ctx, ref, own32, Kc)
+    _compare(case + "_colour", ctx, ref, own32, Kc, names=_names(use_deform, True, split))
     if len(Kt):
         ref, own32 = _reference(("large", name, "tail"), net, x[Kt], d[Kt], t[Kt], False)
-        _compare(case + "_tail", ctx, ref, own32, Kt)
-    _finite(ctx, _names(use_deform, False), M)
+        _compare(case + "_tail", ctx, ref, own32, Kt, names=tail_names or _names(use_deform, False, split))
+    _finite(ctx, _names(use_deform, False, split), M)
     _finite(ctx, ["feat", "rgb"], n_color)
 
 
@@ -342,11 +354,10 @@ def _screened_z(net, rays, zmax, N, n, rng, rows=None):
     raise AssertionError("could not place the samples away from the ReLU kinks")
 
 
-@pytest.mark.parametrize("use_deform", [True, False])
-@pytest.mark.parametrize("n,N", [(1, 77), (32, 7), (64, 5), (100, 7), (128, 3)])
-def test_point_source_ray_samples(n, N, use_deform):
-    """Mode 1: z is a column window [5, 5 + n) of a wider array (ldz = n + 9), n is or is not a multiple of a tile, N n is not a multiple
-    of 128 (n = 128 aside); rays with d.z < 0 and |d.z| = 1e-3."""
+RAY_SAMPLES = [(1, 77), (32, 7), (64, 5), (100, 7), (128, 3)]
+
+
+def _ray_samples(n, N, use_deform, split=False, save=True):
     eng, weff, packed, net = _setup("trained", use_deform)
     rays, zmax, rng = _ray_set(N, 300 + n)
     z, redrawn = _screened_z(net, rays, zmax, N, n, rng)
@@ -356,17 +367,23 @@ def test_point_source_ray_samples(n, N, use_deform):
     rays_d, z_d = rays.cuda().contiguous(), zfull.cuda().contiguous()
     pts = eng.points(rays=rays_d, z=z_d, n_per_ray=n, ldz=ldz)
     pts.z = C.c_void_p(z_d.data_ptr() + 4 * col0)
-    ctx = _launch(eng, weff, packed, pts, _flags(use_deform, True), poison=float("nan"))
+    ctx = _launch(eng, weff, packed, pts, _flags(use_deform, True, save), poison=float("nan"), split=split)
     x, d, t = _ray_points(rays, z)
     ref, own32 = _reference(("mode1", use_deform, n, N), net, x, d, t, True)
-    case = f"A_mode1_{int(use_deform)}_{n}x{N}"
+    case = "X3_" * split + f"A_mode1_{int(use_deform)}_{n}x{N}" + ("" if save else "_nosave")
     _note(case, redrawn=redrawn)
-    _compare(case, ctx, ref, own32, np.arange(N * n))
+    _compare(case, ctx, ref, own32, np.arange(N * n), names=_names(use_deform, True, split))
 
 
 @pytest.mark.parametrize("use_deform", [True, False])
-def test_point_source_samples_then_points_small(use_deform):
-    """Mode 2: 7 x 32 ray samples followed by 37 explicit points, 192 of the samples coloured (the tail holds samples AND points)."""
+@pytest.mark.parametrize("n,N", RAY_SAMPLES)
+def test_point_source_ray_samples(n, N, use_deform):
+    """Mode 1: z is a column window [5, 5 + n) of a wider array (ldz = n + 9), n is or is not a multiple of a tile, N n is not a multiple
+    of 128 (n = 128 aside); rays with d.z < 0 and |d.z| = 1e-3."""
+    _ray_samples(n, N, use_deform)
+
+
+def _samples_then_points_small(use_deform, split=False, save=True):
     eng, weff, packed, net = _setup("trained", use_deform)
     N, n, Ma, mc = 7, 32, 37, 192
     rays, zmax, rng = _ray_set(N, 411)
@@ -376,20 +393,26 @@ def test_point_source_samples_then_points_small(use_deform):
     rays_d, z_d = rays.cuda().contiguous(), z.cuda().contiguous()
     pts = eng.points(rays=rays_d, z=z_d, n_per_ray=n, x=xa.cuda().contiguous(), t=ta.cuda().contiguous())
     assert (pts.mode, pts.M_split, pts.M) == (2, N * n, N * n + Ma)
-    ctx = _launch(eng, weff, packed, pts, _flags(use_deform, True), mc, poison=float("nan"))
+    ctx = _launch(eng, weff, packed, pts, _flags(use_deform, True, save), mc, poison=float("nan"), split=split)
     xs, ds, ts = _ray_points(rays, z)
     dflt = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float64).expand(Ma, 3)          # explicit points of mode 2 carry no direction
     x, d, t = torch.cat([xs, xa.double()]), torch.cat([ds, dflt]), torch.cat([ts, ta.double()])
-    case = f"A_mode2_small_{int(use_deform)}"
+    key = f"A_mode2_small_{int(use_deform)}"
+    case = "X3_" * split + key + ("" if save else "_nosave")
     _note(case, redrawn=redrawn + cnt[0])
-    ref, own32 = _reference((case, "colour"), net, x[:mc], d[:mc], t[:mc], True)
-    _compare(case + "_colour", ctx, ref, own32, np.arange(mc))
-    ref, own32 = _reference((case, "tail"), net, x[mc:], d[mc:], t[mc:], False)
-    _compare(case + "_tail", ctx, ref, own32, np.arange(mc, N * n + Ma))
+    ref, own32 = _reference((key, "colour"), net, x[:mc], d[:mc], t[:mc], True)
+    _compare(case + "_colour", ctx, ref, own32, np.arange(mc), names=_names(use_deform, True, split))
+    ref, own32 = _reference((key, "tail"), net, x[mc:], d[mc:], t[mc:], False)
+    _compare(case + "_tail", ctx, ref, own32, np.arange(mc, N * n + Ma), names=_names(use_deform, False, split))
 
 
-def test_point_source_training_step_layout():
-    """Mode 2 at the size of every training step: 1 024 x 64 ray samples (all coloured) followed by 3 072 explicit points."""
+@pytest.mark.parametrize("use_deform", [True, False])
+def test_point_source_samples_then_points_small(use_deform):
+    """Mode 2: 7 x 32 ray samples followed by 37 explicit points, 192 of the samples coloured (the tail holds samples AND points)."""
+    _samples_then_points_small(use_deform)
+
+
+def _training_step_layout(split=False, save=True, tail_names=None):
     eng, weff, packed, net = _setup("trained", True)
     N, n, Ma = 1024, 64, 3072
     M = N * n + Ma
@@ -401,22 +424,26 @@ def test_point_source_training_step_layout():
     cnt = [0]
     xa, _, ta, *_ = inputs(Ma, 422, True, screen=Ka, count=cnt)
     pts = eng.points(rays=rays.cuda().contiguous(), z=z.cuda().contiguous(), n_per_ray=n, x=xa.cuda().contiguous(), t=ta.cuda().contiguous())
-    ctx = _launch(eng, weff, packed, pts, _flags(True, True), N * n)
+    ctx = _launch(eng, weff, packed, pts, _flags(True, True, save), N * n, split=split)
     xs, ds, ts = _ray_points(rays, z)
-    case = "A_mode2_train"
+    key = "A_mode2_train"
+    case = "X3_" * split + key + ("" if save else "_nosave")
     _note(case, redrawn=redrawn + cnt[0])
-    ref, own32 = _reference((case, "colour"), net, xs[Ks], ds[Ks], ts[Ks], True)
-    _compare(case + "_colour", ctx, ref, own32, Ks)
+    ref, own32 = _reference((key, "colour"), net, xs[Ks], ds[Ks], ts[Ks], True)
+    _compare(case + "_colour", ctx, ref, own32, Ks, names=_names(True, True, split))
     dflt = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float64).expand(len(Ka), 3)
-    ref, own32 = _reference((case, "tail"), net, xa[Ka].double(), dflt, ta[Ka].double(), False)
-    _compare(case + "_tail", ctx, ref, own32, Ka + N * n)
-    _finite(ctx, _names(True, False), M)
+    ref, own32 = _reference((key, "tail"), net, xa[Ka].double(), dflt, ta[Ka].double(), False)
+    _compare(case + "_tail", ctx, ref, own32, Ka + N * n, names=tail_names or _names(True, False, split))
+    _finite(ctx, _names(True, False, split), M)
     _finite(ctx, ["feat", "rgb"], N * n)
 
 
-@pytest.mark.parametrize("use_deform", [True, False])
-def test_point_source_shared_time(use_deform):
-    """Mode 0 with t_scalar = 1: one time value for all 333 points (renderonpts' shared-time form)."""
+def test_point_source_training_step_layout():
+    """Mode 2 at the size of every training step: 1 024 x 64 ray samples (all coloured) followed by 3 072 explicit points."""
+    _training_step_layout()
+
+
+def _shared_time(use_deform, split=False, save=True):
     eng, weff, packed, net = _setup("trained", use_deform)
     M, rng = 333, np.random.default_rng(431)
     t0 = torch.tensor([0.3125])
@@ -432,10 +459,17 @@ def test_point_source_shared_time(use_deform):
         raise AssertionError("could not place the points away from the ReLU kinks")
     pts = eng.points(x=x.cuda().contiguous(), t=t0.cuda(), dirs=d.cuda().contiguous())
     assert pts.t_scalar == 1
-    ctx = _launch(eng, weff, packed, pts, _flags(use_deform, True), poison=float("nan"))
+    ctx = _launch(eng, weff, packed, pts, _flags(use_deform, True, save), poison=float("nan"), split=split)
     ref, own32 = _reference(("tscalar", use_deform), net, x, d, t0.expand(M), True)
-    _note(f"A_tscalar_{int(use_deform)}", redrawn=redrawn)
-    _compare(f"A_tscalar_{int(use_deform)}", ctx, ref, own32, np.arange(M))
+    case = "X3_" * split + f"A_tscalar_{int(use_deform)}" + ("" if save else "_nosave")
+    _note(case, redrawn=redrawn)
+    _compare(case, ctx, ref, own32, np.arange(M), names=_names(use_deform, True, split))
+
+
+@pytest.mark.parametrize("use_deform", [True, False])
+def test_point_source_shared_time(use_deform):
+    """Mode 0 with t_scalar = 1: one time value for all 333 points (renderonpts' shared-time form)."""
+    _shared_time(use_deform)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 """GPU parity of the OPT-IN split-precision inference kernels (csrc/infer_x3r.hip: deformation value + tangent pass and VJP sweep, SDF value +
 geometry features + reverse sweep on the bf16 matrix pipes with exactly split fp32 operands) -- held to the SAME budgets as the fp32 kernels
-(tests/test_gpu_point.py) against the fp64 oracle and the per-point vectors captured from the reference."""
+(tests/test_gpu_point.py) against the fp64 oracle and the per-point vectors captured from the reference.  The points here are not
+screened away from the ReLU kinks, hence the quantile gates; every row with maximum gates, at the family's tile edges and launch
+layouts: tests/test_gpu_forward_shapes_x3.py (forward, queries, ray marching) and tests/test_gpu_backward_shapes_x3.py (backward)."""
 import numpy as np
 import pytest
 import torch
