@@ -6,9 +6,8 @@
 //   k_band_lattice_points  coordinates of a run of lattice points (stride 1: the lattice itself; stride B: the coarse lattice)
 //   k_band_seed            round[b] = 1 for a seed block (corner flags differ | a NaN corner | no corner farther than ``margin`` from the
 //                          level), else 0; fill[b] = the corner value farthest from the level
-//   k_band_blocksum / k_band_scan_blocks / k_band_compact
-//                          the blocks with round[b] == r in ascending order -> ids[], exclusive point offsets poff[], totals (iso.hip's
-//                          three-launch scan, over blocks)
+//   scan.h's three         the blocks with round[b] == r in ascending order -> ids[], exclusive point offsets poff[], totals (BandSrc:
+//                          the scan over blocks, its store pass compacting)
 //   k_band_fill            field[p] = fill[block of p]
 //   k_band_points          coordinates of points [m0, m0 + count) of the listed blocks (closed ranges: shared faces are listed twice)
 //   k_band_scatter         their values -> field
@@ -27,10 +26,7 @@
 
 namespace es {
 
-constexpr int BAND_PER_THREAD = 16;                          // consecutive blocks of one thread of the scan kernels
-constexpr int BAND_CHUNK = 256 * BAND_PER_THREAD;            // blocks per scan workgroup
 constexpr long long BAND_MAX_POINTS = 1ll << 31;             // int32 indices
-constexpr unsigned BAND_MAX_GRID = 1u << 16;                 // grid-stride launches
 
 struct BandGeom {
     int nx, ny, nz, B, nbx, nby, nbz;
@@ -44,9 +40,8 @@ struct BandScratch {
     int* poff;               // [NB] first point of each listed block
     int* bsum;               // [nchunk][2] listed blocks / their points per chunk
     int* boff;               // [nchunk][2] exclusive scan of bsum
-    int nchunk;
+    long long nchunk, bytes;
 };
-static inline long long band_up16(long long b) { return (b + 15) / 16 * 16; }
 static inline BandGeom band_geom(int nx, int ny, int nz, int B) {
     BandGeom g;
     g.nx = nx; g.ny = ny; g.nz = nz; g.B = B;
@@ -55,20 +50,17 @@ static inline BandGeom band_geom(int nx, int ny, int nz, int B) {
     g.N = (long long)nx * ny * nz;
     return g;
 }
-static inline long long band_scratch_bytes(const BandGeom& g) {
-    const long long nchunk = (g.NB + BAND_CHUNK - 1) / BAND_CHUNK;
-    return 4 * band_up16(4ll * g.NB) + 2 * band_up16(8 * nchunk);
-}
-static inline BandScratch band_carve(void* scratch, const BandGeom& g) {
+static BandScratch band_layout(const void* scratch, const BandGeom& g) {          // a null scratch measures only
+    Carver c(scratch);
     BandScratch s;
-    s.nchunk = (g.NB + BAND_CHUNK - 1) / BAND_CHUNK;
-    char* p = static_cast<char*>(scratch);
-    s.round = reinterpret_cast<int*>(p); p += band_up16(4ll * g.NB);
-    s.fill = reinterpret_cast<float*>(p); p += band_up16(4ll * g.NB);
-    s.ids = reinterpret_cast<int*>(p); p += band_up16(4ll * g.NB);
-    s.poff = reinterpret_cast<int*>(p); p += band_up16(4ll * g.NB);
-    s.bsum = reinterpret_cast<int*>(p); p += band_up16(8ll * s.nchunk);
-    s.boff = reinterpret_cast<int*>(p);
+    s.nchunk = scan_chunks(g.NB);
+    s.round = c.take<int>(g.NB);          // (first: Engine.band_field reads it from the head of the scratch)
+    s.fill = c.take<float>(g.NB);
+    s.ids = c.take<int>(g.NB);
+    s.poff = c.take<int>(g.NB);
+    s.bsum = c.take<int>(2 * s.nchunk);
+    s.boff = c.take<int>(2 * s.nchunk);
+    s.bytes = c.off;
     return s;
 }
 
@@ -124,59 +116,32 @@ __global__ __launch_bounds__(256) void k_band_seed(const float* __restrict__ uc,
     }
 }
 
-// a thread's 16 consecutive blocks: how many are listed (round == sel) and the points of those
-__device__ __forceinline__ void band_chunk_counts(const int* __restrict__ round, const BandGeom& g, int sel, int b0, int& cnt, int& pts,
-                                                  unsigned& mask) {
-    cnt = 0; pts = 0; mask = 0;
+// the scan's source: the blocks with round == sel, in ascending order -> ids[], poff[]
+struct BandSrc {
+    using sum_t = int;
+    using items_t = unsigned;          // bit i: block b0 + i is listed
+    const int* round;
+    BandGeom g;
+    int sel;
+    int *ids, *poff;
+    // a thread's 16 consecutive blocks: how many are listed and the points of those
+    __device__ __forceinline__ void load(long long b0, unsigned& mask, int& cnt, int& pts) const {
+        cnt = 0; pts = 0; mask = 0;
 #pragma unroll
-    for (int i = 0; i < BAND_PER_THREAD; ++i) {
-        const int b = b0 + i;
-        if (b < g.NB && round[b] == sel) { ++cnt; pts += band_block_points(g, b); mask |= 1u << i; }
+        for (int i = 0; i < SCAN_PER_THREAD; ++i) {
+            const int b = (int)b0 + i;
+            if (b < g.NB && round[b] == sel) { ++cnt; pts += band_block_points(g, b); mask |= 1u << i; }
+        }
     }
-}
-
-__global__ __launch_bounds__(256) void k_band_blocksum(const int* __restrict__ round, BandGeom g, int sel, int* __restrict__ bsum) {
-    __shared__ int part[4][2];
-    int cnt, pts;
-    unsigned mask;
-    band_chunk_counts(round, g, sel, blockIdx.x * BAND_CHUNK + threadIdx.x * BAND_PER_THREAD, cnt, pts, mask);
-    int total[2];
-    block_scan2(cnt, pts, part, total);
-    if (threadIdx.x == 0) { bsum[2 * (size_t)blockIdx.x] = total[0]; bsum[2 * (size_t)blockIdx.x + 1] = total[1]; }
-}
-
-// One workgroup: thread i owns a contiguous run of chunks (iso.hip k_iso_scan_blocks).
-__global__ __launch_bounds__(256) void k_band_scan_blocks(const int* __restrict__ bsum, int nchunk, int* __restrict__ boff, long long* __restrict__ totals) {
-    __shared__ long long part[4][2];
-    const int per = (nchunk + 255) / 256, c0 = threadIdx.x * per, c1 = c0 + per < nchunk ? c0 + per : nchunk;
-    long long sc = 0, sp = 0;
-    for (int c = c0; c < c1; ++c) { sc += bsum[2 * c]; sp += bsum[2 * c + 1]; }
-    long long total[2];
-    block_scan2(sc, sp, part, total);
-    for (int c = c0; c < c1; ++c) {
-        boff[2 * c] = (int)sc; boff[2 * c + 1] = (int)sp;
-        sc += bsum[2 * c]; sp += bsum[2 * c + 1];
-    }
-    if (threadIdx.x == 0) { totals[0] = total[0]; totals[1] = total[1]; }
-}
-
-__global__ __launch_bounds__(256) void k_band_compact(const int* __restrict__ round, BandGeom g, int sel, const int* __restrict__ boff,
-                                                      int* __restrict__ ids, int* __restrict__ poff) {
-    __shared__ int part[4][2];
-    const int b0 = blockIdx.x * BAND_CHUNK + threadIdx.x * BAND_PER_THREAD;
-    int cnt, pts;
-    unsigned mask;
-    band_chunk_counts(round, g, sel, b0, cnt, pts, mask);
-    int total[2];
-    block_scan2(cnt, pts, part, total);
-    cnt += boff[2 * (size_t)blockIdx.x]; pts += boff[2 * (size_t)blockIdx.x + 1];
+    __device__ __forceinline__ void store(long long b0, const unsigned& mask, int cnt, int pts) const {
 #pragma unroll
-    for (int i = 0; i < BAND_PER_THREAD; ++i) {
-        if (!((mask >> i) & 1u)) continue;
-        if (cnt >= 0 && cnt < g.NB) { ids[cnt] = b0 + i; poff[cnt] = pts; }
-        ++cnt; pts += band_block_points(g, b0 + i);
+        for (int i = 0; i < SCAN_PER_THREAD; ++i) {
+            if (!((mask >> i) & 1u)) continue;
+            if (cnt >= 0 && cnt < g.NB) { ids[cnt] = (int)b0 + i; poff[cnt] = pts; }
+            ++cnt; pts += band_block_points(g, (int)b0 + i);
+        }
     }
-}
+};
 
 __global__ __launch_bounds__(256) void k_band_fill(BandGeom g, const float* __restrict__ fill, float* __restrict__ field) {
     for (long long p = blockIdx.x * 256ll + threadIdx.x; p < g.N; p += gridDim.x * 256ll) {
@@ -270,30 +235,20 @@ static int band_check(int nx, int ny, int nz, int block) {
     ES_REQUIRE(nb * (block + 1) * (block + 1) * (block + 1) < BAND_MAX_POINTS, "band blocks hold 2^31 points or more (int32 indices)");
     return ST_OK;
 }
-static inline unsigned band_grid(long long n, int per_wg = 256) {
-    const long long wg = (n + per_wg - 1) / per_wg;
-    return (unsigned)(wg < 1 ? 1 : (wg < BAND_MAX_GRID ? wg : BAND_MAX_GRID));
-}
 // the list of the blocks with round == sel (ids, poff) and its totals
-static int band_list(const BandGeom& g, const BandScratch& s, int sel, long long* totals, hipStream_t st) {
-    hipLaunchKernelGGL(k_band_blocksum, dim3((unsigned)s.nchunk), dim3(256), 0, st, s.round, g, sel, s.bsum);
-    hipLaunchKernelGGL(k_band_scan_blocks, dim3(1), dim3(256), 0, st, s.bsum, s.nchunk, s.boff, totals);
-    hipLaunchKernelGGL(k_band_compact, dim3((unsigned)s.nchunk), dim3(256), 0, st, s.round, g, sel, s.boff, s.ids, s.poff);
-    return ST_OK;
+static void band_list(const BandGeom& g, const BandScratch& s, int sel, long long* totals, hipStream_t st) {
+    scan_launch(BandSrc{s.round, g, sel, s.ids, s.poff}, s.nchunk, s.bsum, s.boff, totals, st);
 }
 
 }  // namespace es
 
 using namespace es;
 
-#define BAND_SCRATCH_OK(scratch) \
-    ES_REQUIRE(scratch && reinterpret_cast<uintptr_t>(scratch) % 16 == 0, "band scratch must be a 16-byte aligned device buffer")
-
 extern "C" {
 
 int64_t es_band_scratch_bytes(int nx, int ny, int nz, int block) {
     if (band_check(nx, ny, nz, block) != ST_OK) return -1;
-    return band_scratch_bytes(band_geom(nx, ny, nz, block));
+    return band_layout(nullptr, band_geom(nx, ny, nz, block)).bytes;
 }
 
 int es_band_lattice_points(const float* ax, const float* ay, const float* az, int nx, int ny, int nz, int stride, long long p0, long long count,
@@ -306,7 +261,7 @@ int es_band_lattice_points(const float* ax, const float* ay, const float* az, in
     ES_REQUIRE(p0 >= 0 && count >= 0 && p0 + count <= (long long)cx * cy * cz, "es_band_lattice_points: point range outside the lattice");
     if (count == 0) return ST_OK;
     ES_REQUIRE(ax && ay && az && x, "es_band_lattice_points needs the three axes and x");
-    hipLaunchKernelGGL(k_band_lattice_points, dim3(band_grid(count)), dim3(256), 0, static_cast<hipStream_t>(stream), ax, ay, az, nx, ny, nz, cx, cy, cz,
+    hipLaunchKernelGGL(k_band_lattice_points, dim3(grid_for(count)), dim3(256), 0, static_cast<hipStream_t>(stream), ax, ay, az, nx, ny, nz, cx, cy, cz,
                        stride, p0, count, x);
     return hip_last("es_band_lattice_points");
 }
@@ -315,11 +270,11 @@ int es_band_seed(const float* coarse, int nx, int ny, int nz, int block, double 
                  void* stream) {
     if (const int s = band_check(nx, ny, nz, block)) return s;
     ES_REQUIRE(coarse && totals, "es_band_seed needs coarse and totals");
-    BAND_SCRATCH_OK(scratch);
+    ES_SCRATCH_OK(scratch, "band scratch");
     const BandGeom g = band_geom(nx, ny, nz, block);
-    const BandScratch s = band_carve(scratch, g);
+    const BandScratch s = band_layout(scratch, g);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(k_band_seed, dim3(band_grid(g.NB)), dim3(256), 0, st, coarse, g, threshold, margin, s.round, s.fill);
+    hipLaunchKernelGGL(k_band_seed, dim3(grid_for(g.NB)), dim3(256), 0, st, coarse, g, threshold, margin, s.round, s.fill);
     band_list(g, s, 1, totals, st);
     return hip_last("es_band_seed");
 }
@@ -327,23 +282,23 @@ int es_band_seed(const float* coarse, int nx, int ny, int nz, int block, double 
 int es_band_fill(int nx, int ny, int nz, int block, const void* scratch, float* field, void* stream) {
     if (const int s = band_check(nx, ny, nz, block)) return s;
     ES_REQUIRE(field, "es_band_fill needs field");
-    BAND_SCRATCH_OK(scratch);
+    ES_SCRATCH_OK(scratch, "band scratch");
     const BandGeom g = band_geom(nx, ny, nz, block);
-    const BandScratch s = band_carve(const_cast<void*>(scratch), g);
-    hipLaunchKernelGGL(k_band_fill, dim3(band_grid(g.N)), dim3(256), 0, static_cast<hipStream_t>(stream), g, s.fill, field);
+    const BandScratch s = band_layout(scratch, g);
+    hipLaunchKernelGGL(k_band_fill, dim3(grid_for(g.N)), dim3(256), 0, static_cast<hipStream_t>(stream), g, s.fill, field);
     return hip_last("es_band_fill");
 }
 
 int es_band_points(const float* ax, const float* ay, const float* az, int nx, int ny, int nz, int block, const void* scratch, long long n_list,
                    long long m0, long long count, float* x, void* stream) {
     if (const int s = band_check(nx, ny, nz, block)) return s;
-    BAND_SCRATCH_OK(scratch);
+    ES_SCRATCH_OK(scratch, "band scratch");
     const BandGeom g = band_geom(nx, ny, nz, block);
     ES_REQUIRE(n_list >= 1 && n_list <= g.NB && m0 >= 0 && count >= 0 && m0 + count < BAND_MAX_POINTS, "es_band_points: list or point range out of range");
     if (count == 0) return ST_OK;
     ES_REQUIRE(ax && ay && az && x, "es_band_points needs the three axes and x");
-    const BandScratch s = band_carve(const_cast<void*>(scratch), g);
-    hipLaunchKernelGGL(k_band_points, dim3(band_grid(count)), dim3(256), 0, static_cast<hipStream_t>(stream), ax, ay, az, g, s.ids, s.poff, (int)n_list, m0,
+    const BandScratch s = band_layout(scratch, g);
+    hipLaunchKernelGGL(k_band_points, dim3(grid_for(count)), dim3(256), 0, static_cast<hipStream_t>(stream), ax, ay, az, g, s.ids, s.poff, (int)n_list, m0,
                        count, x);
     return hip_last("es_band_points");
 }
@@ -351,13 +306,13 @@ int es_band_points(const float* ax, const float* ay, const float* az, int nx, in
 int es_band_scatter(const float* values, int nx, int ny, int nz, int block, const void* scratch, long long n_list, long long m0, long long count,
                     float* field, void* stream) {
     if (const int s = band_check(nx, ny, nz, block)) return s;
-    BAND_SCRATCH_OK(scratch);
+    ES_SCRATCH_OK(scratch, "band scratch");
     const BandGeom g = band_geom(nx, ny, nz, block);
     ES_REQUIRE(n_list >= 1 && n_list <= g.NB && m0 >= 0 && count >= 0 && m0 + count < BAND_MAX_POINTS, "es_band_scatter: list or point range out of range");
     if (count == 0) return ST_OK;
     ES_REQUIRE(values && field, "es_band_scatter needs values and field");
-    const BandScratch s = band_carve(const_cast<void*>(scratch), g);
-    hipLaunchKernelGGL(k_band_scatter, dim3(band_grid(count)), dim3(256), 0, static_cast<hipStream_t>(stream), values, g, s.ids, s.poff, (int)n_list, m0,
+    const BandScratch s = band_layout(scratch, g);
+    hipLaunchKernelGGL(k_band_scatter, dim3(grid_for(count)), dim3(256), 0, static_cast<hipStream_t>(stream), values, g, s.ids, s.poff, (int)n_list, m0,
                        count, field);
     return hip_last("es_band_scatter");
 }
@@ -366,11 +321,11 @@ int es_band_grow(const float* field, int nx, int ny, int nz, int block, double t
     if (const int s = band_check(nx, ny, nz, block)) return s;
     ES_REQUIRE(field && totals, "es_band_grow needs field and totals");
     ES_REQUIRE(round >= 1 && round < (1 << 30), "es_band_grow: round must be >= 1");
-    BAND_SCRATCH_OK(scratch);
+    ES_SCRATCH_OK(scratch, "band scratch");
     const BandGeom g = band_geom(nx, ny, nz, block);
-    const BandScratch s = band_carve(scratch, g);
+    const BandScratch s = band_layout(scratch, g);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(k_band_grow, dim3(band_grid(g.NB, 4)), dim3(256), 0, st, field, g, threshold, round, s.round, s.fill);
+    hipLaunchKernelGGL(k_band_grow, dim3(grid_for(g.NB, 4)), dim3(256), 0, st, field, g, threshold, round, s.round, s.fill);
     band_list(g, s, round + 1, totals, st);
     return hip_last("es_band_grow");
 }

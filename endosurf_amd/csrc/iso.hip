@@ -6,9 +6,7 @@
 // owner slot (p, d) and welding is indexing: vertex id = (exclusive scan of the owners' crossing-edge counts)[p] + rank of d inside p's
 // 7-bit mask.  Five launches, no atomics, no hand-off between workgroups inside a launch (bit-identical from call to call):
 //   k_iso_classify     code[p] = mask of crossing owned edges | triangles of cell p << 8   (corner signs through an LDS tile)
-//   k_iso_blocksum     per 4096-point chunk: sum of the vertex and triangle counts
-//   k_iso_scan_blocks  exclusive scan of the chunk sums (one workgroup), totals
-//   k_iso_offsets      per chunk: exclusive scan + chunk offset -> voff[p], toff[p]
+//   scan.h's three     exclusive scan of the vertex and triangle counts of the codes -> voff[p], toff[p], totals (IsoSrc)
 //   k_iso_emit         vertices (fp64 interpolation, stored fp32), their end points, triangles
 // Vertex order = ascending (linear id of the owner point, d); triangle order = ascending (cell, tetrahedron, table order).
 #include <hip/hip_runtime.h>
@@ -23,8 +21,6 @@
 namespace es {
 
 constexpr int ISO_TX = 4, ISO_TY = 8, ISO_TZ = 64;          // classify tile (z fastest, one wave per x row)
-constexpr int ISO_PER_THREAD = 16;                          // consecutive points of one thread of the scan kernels
-constexpr int ISO_CHUNK = 256 * ISO_PER_THREAD;             // points per scan workgroup
 constexpr long long ISO_MAX_POINTS = 1ll << 31;             // int32 indices
 
 struct IsoScratch {
@@ -33,23 +29,19 @@ struct IsoScratch {
     int* bsum;               // [nblk][2] vertex / triangle count of a chunk
     int* boff;               // [nblk][2] exclusive scan of bsum
     unsigned short* code;    // [N] classify output
-    long long N, nblk;
+    long long N, nblk, bytes;
 };
-static inline long long up16(long long b) { return (b + 15) / 16 * 16; }
-static inline long long iso_scratch_bytes(long long N) {
-    const long long nblk = (N + ISO_CHUNK - 1) / ISO_CHUNK;
-    return 2 * up16(4 * N) + 2 * up16(8 * nblk) + up16(2 * N);
-}
-static inline IsoScratch iso_carve(void* scratch, long long N) {
+static IsoScratch iso_layout(const void* scratch, long long N) {          // a null scratch measures only
+    Carver c(scratch);
     IsoScratch s;
     s.N = N;
-    s.nblk = (N + ISO_CHUNK - 1) / ISO_CHUNK;
-    char* p = static_cast<char*>(scratch);
-    s.voff = reinterpret_cast<int*>(p); p += up16(4 * N);
-    s.toff = reinterpret_cast<int*>(p); p += up16(4 * N);
-    s.bsum = reinterpret_cast<int*>(p); p += up16(8 * s.nblk);
-    s.boff = reinterpret_cast<int*>(p); p += up16(8 * s.nblk);
-    s.code = reinterpret_cast<unsigned short*>(p);
+    s.nblk = scan_chunks(N);
+    s.voff = c.take<int>(N);
+    s.toff = c.take<int>(N);
+    s.bsum = c.take<int>(2 * s.nblk);
+    s.boff = c.take<int>(2 * s.nblk);
+    s.code = c.take<unsigned short>(N);
+    s.bytes = c.off;
     return s;
 }
 
@@ -109,66 +101,37 @@ __global__ __launch_bounds__(256) void k_iso_classify(const float* __restrict__ 
     }
 }
 
-// the 16 codes of a thread's consecutive points (0 beyond the grid) -> its vertex and triangle counts
-__device__ __forceinline__ void chunk_load(const unsigned short* __restrict__ code, long long N, long long p0, unsigned short (&c)[ISO_PER_THREAD]) {
-    if (p0 + ISO_PER_THREAD <= N) {
-        const uint4* q = reinterpret_cast<const uint4*>(code + p0);          // 32-byte aligned: code is 16-byte aligned, p0 a multiple of 16
-        uint4 w[2] = {q[0], q[1]};
-        __builtin_memcpy(c, w, sizeof(c));
-    } else {
-#pragma unroll
-        for (int i = 0; i < ISO_PER_THREAD; ++i) c[i] = p0 + i < N ? code[p0 + i] : (unsigned short)0;
-    }
-}
 __device__ __forceinline__ int code_verts(unsigned c) { return __popc(c & 0x7fu); }
 __device__ __forceinline__ int code_tris(unsigned c) { return (int)((c >> 8) & 15u); }
-
-__global__ __launch_bounds__(256) void k_iso_blocksum(const unsigned short* __restrict__ code, long long N, int* __restrict__ bsum) {
-    __shared__ int part[4][2];
-    unsigned short c[ISO_PER_THREAD];
-    chunk_load(code, N, (long long)blockIdx.x * ISO_CHUNK + threadIdx.x * ISO_PER_THREAD, c);
-    int nv = 0, nt = 0;
+// the scan's source: the codes -> voff[p], toff[p]
+struct IsoSrc {
+    using sum_t = int;
+    using items_t = unsigned short[SCAN_PER_THREAD];
+    const unsigned short* code;
+    long long N;
+    int *voff, *toff;
+    // the 16 codes of a thread's consecutive points (0 beyond the grid) -> its vertex and triangle counts
+    __device__ __forceinline__ void load(long long p0, items_t& c, int& nv, int& nt) const {
+        if (p0 + SCAN_PER_THREAD <= N) {
+            const uint4* q = reinterpret_cast<const uint4*>(code + p0);          // 32-byte aligned: code is 16-byte aligned, p0 a multiple of 16
+            uint4 w[2] = {q[0], q[1]};
+            __builtin_memcpy(c, w, sizeof(c));
+        } else {
 #pragma unroll
-    for (int i = 0; i < ISO_PER_THREAD; ++i) { nv += code_verts(c[i]); nt += code_tris(c[i]); }
-    int total[2];
-    block_scan2(nv, nt, part, total);
-    if (threadIdx.x == 0) { bsum[2 * (size_t)blockIdx.x] = total[0]; bsum[2 * (size_t)blockIdx.x + 1] = total[1]; }
-}
-
-// One workgroup: thread i owns a contiguous run of chunks.  Offsets are kept in 64 bits (the totals may exceed int32: the caller must
-// look at them before it emits) and stored truncated.
-__global__ __launch_bounds__(256) void k_iso_scan_blocks(const int* __restrict__ bsum, long long nblk, int* __restrict__ boff, long long* __restrict__ totals) {
-    __shared__ long long part[4][2];
-    const long long per = (nblk + 255) / 256, b0 = threadIdx.x * per, b1 = b0 + per < nblk ? b0 + per : nblk;
-    long long sv = 0, st = 0;
-    for (long long b = b0; b < b1; ++b) { sv += bsum[2 * b]; st += bsum[2 * b + 1]; }
-    long long total[2];
-    block_scan2(sv, st, part, total);
-    for (long long b = b0; b < b1; ++b) {
-        boff[2 * b] = (int)sv; boff[2 * b + 1] = (int)st;
-        sv += bsum[2 * b]; st += bsum[2 * b + 1];
+            for (int i = 0; i < SCAN_PER_THREAD; ++i) c[i] = p0 + i < N ? code[p0 + i] : (unsigned short)0;
+        }
+        nv = 0; nt = 0;
+#pragma unroll
+        for (int i = 0; i < SCAN_PER_THREAD; ++i) { nv += code_verts(c[i]); nt += code_tris(c[i]); }
     }
-    if (threadIdx.x == 0) { totals[0] = total[0]; totals[1] = total[1]; }
-}
-
-__global__ __launch_bounds__(256) void k_iso_offsets(const unsigned short* __restrict__ code, long long N, const int* __restrict__ boff,
-                                                     int* __restrict__ voff, int* __restrict__ toff) {
-    __shared__ int part[4][2];
-    unsigned short c[ISO_PER_THREAD];
-    const long long p0 = (long long)blockIdx.x * ISO_CHUNK + threadIdx.x * ISO_PER_THREAD;
-    chunk_load(code, N, p0, c);
-    int nv = 0, nt = 0;
+    __device__ __forceinline__ void store(long long p0, const items_t& c, int nv, int nt) const {
 #pragma unroll
-    for (int i = 0; i < ISO_PER_THREAD; ++i) { nv += code_verts(c[i]); nt += code_tris(c[i]); }
-    int total[2];
-    block_scan2(nv, nt, part, total);
-    nv += boff[2 * (size_t)blockIdx.x]; nt += boff[2 * (size_t)blockIdx.x + 1];
-#pragma unroll
-    for (int i = 0; i < ISO_PER_THREAD; ++i) {
-        if (p0 + i < N) { voff[p0 + i] = nv; toff[p0 + i] = nt; }
-        nv += code_verts(c[i]); nt += code_tris(c[i]);
+        for (int i = 0; i < SCAN_PER_THREAD; ++i) {
+            if (p0 + i < N) { voff[p0 + i] = nv; toff[p0 + i] = nt; }
+            nv += code_verts(c[i]); nt += code_tris(c[i]);
+        }
     }
-}
+};
 
 // One thread per grid point: the vertices it owns and the triangles of its cell.  Every read is inside the grid whatever ``code`` /
 // ``voff`` / ``toff`` hold (validity comes from the coordinates), every write is checked against the capacity of the output buffers.
@@ -240,22 +203,20 @@ extern "C" {
 
 int64_t es_iso_scratch_bytes(int nx, int ny, int nz) {
     if (iso_check_dims(nx, ny, nz) != ST_OK) return -1;
-    return iso_scratch_bytes((long long)nx * ny * nz);
+    return iso_layout(nullptr, (long long)nx * ny * nz).bytes;
 }
 
 int es_iso_count(const float* field, int nx, int ny, int nz, double threshold, void* scratch, long long* totals, void* stream) {
     if (const int s = iso_check_dims(nx, ny, nz)) return s;
     ES_REQUIRE(field && scratch && totals, "es_iso_count needs field, scratch and totals");
-    ES_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 16 == 0, "iso-surface scratch must be 16-byte aligned");
+    ES_SCRATCH_OK(scratch, "iso-surface scratch");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const IsoScratch s = iso_carve(scratch, (long long)nx * ny * nz);
+    const IsoScratch s = iso_layout(scratch, (long long)nx * ny * nz);
     const int tiles_z = (nz + ISO_TZ - 1) / ISO_TZ, tiles_y = (ny + ISO_TY - 1) / ISO_TY, tiles_x = (nx + ISO_TX - 1) / ISO_TX;
     const long long ntiles = (long long)tiles_z * tiles_y * tiles_x;
     const unsigned grid = (unsigned)(ntiles < (1ll << 20) ? ntiles : (1ll << 20));
     hipLaunchKernelGGL(k_iso_classify, dim3(grid), dim3(256), 0, st, field, nx, ny, nz, threshold, tiles_z, tiles_y, ntiles, s.code);
-    hipLaunchKernelGGL(k_iso_blocksum, dim3((unsigned)s.nblk), dim3(256), 0, st, s.code, s.N, s.bsum);
-    hipLaunchKernelGGL(k_iso_scan_blocks, dim3(1), dim3(256), 0, st, s.bsum, s.nblk, s.boff, totals);
-    hipLaunchKernelGGL(k_iso_offsets, dim3((unsigned)s.nblk), dim3(256), 0, st, s.code, s.N, s.boff, s.voff, s.toff);
+    scan_launch(IsoSrc{s.code, s.N, s.voff, s.toff}, s.nblk, s.bsum, s.boff, totals, st);
     return hip_last("es_iso_count");
 }
 
@@ -263,12 +224,12 @@ int es_iso_emit(const float* field, int nx, int ny, int nz, double threshold, co
                 int* edge_ends, int* tris, void* stream) {
     if (const int s = iso_check_dims(nx, ny, nz)) return s;
     ES_REQUIRE(field && scratch, "es_iso_emit needs field and scratch");
-    ES_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 16 == 0, "iso-surface scratch must be 16-byte aligned");
+    ES_SCRATCH_OK(scratch, "iso-surface scratch");
     ES_REQUIRE(n_verts >= 0 && n_tris >= 0 && n_verts < ISO_MAX_POINTS && n_tris < ISO_MAX_POINTS, "mesh does not fit int32 indices");
     if (n_verts == 0 && n_tris == 0) return ST_OK;
     ES_REQUIRE((n_verts == 0 || (verts && edge_ends)) && (n_tris == 0 || tris), "es_iso_emit needs verts, edge_ends and tris");
     const long long N = (long long)nx * ny * nz;
-    const IsoScratch s = iso_carve(const_cast<void*>(scratch), N);
+    const IsoScratch s = iso_layout(scratch, N);
     hipLaunchKernelGGL(k_iso_emit, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), field, nx, ny, nz, threshold,
                        s.code, s.voff, s.toff, (int)n_verts, (int)n_tris, verts, edge_ends, tris);
     return hip_last("es_iso_emit");

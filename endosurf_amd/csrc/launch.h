@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 
@@ -33,6 +34,31 @@ inline int hip_last(const char* what) {
     do {                                                                  \
         if (!(cond)) return ::es::fail(::es::ST_BAD_ARG, msg, #cond);     \
     } while (0)
+
+// a caller's scratch buffer: the regions below are carved at multiples of 16 bytes (uint4 loads rely on it)
+#define ES_SCRATCH_OK(ptr, what) \
+    ES_REQUIRE(ptr && reinterpret_cast<uintptr_t>(ptr) % 16 == 0, what " must be a 16-byte aligned device buffer")
+
+constexpr unsigned MAX_GRID = 1u << 16;          // workgroups of a grid-stride launch
+inline unsigned grid_for(long long n, int per_wg = 256) {
+    const long long wg = (n + per_wg - 1) / per_wg;
+    return (unsigned)(wg < 1 ? 1 : (wg < MAX_GRID ? wg : MAX_GRID));
+}
+
+inline long long up16(long long b) { return (b + 15) / 16 * 16; }
+// A scratch layout is written once, as a sequence of take() calls: with the caller's buffer it carves, with a null base it only
+// measures, so the size a caller is told and the pointers the kernels get cannot disagree.
+struct Carver {
+    char* base;
+    long long off = 0;
+    explicit Carver(const void* scratch) : base(static_cast<char*>(const_cast<void*>(scratch))) {}
+    template <class T>
+    T* take(long long n) {
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += up16((long long)sizeof(T) * n);
+        return p;
+    }
+};
 
 // opt a kernel into > 64 KiB of dynamic LDS (once per kernel)
 template <class K>

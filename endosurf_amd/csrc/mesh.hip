@@ -10,10 +10,10 @@
 //   k_mesh_label         triangle_label, component_triangles (one integer add per distinct label of a wave), the degenerate count
 //   k_mesh_stats         components with a triangle, the largest triangle count
 //   k_mesh_keep_flags    triangle kept / vertex used bytes (the fp64 comparison of the reference's numpy line)
-//   k_mesh_keep_blocksum / k_mesh_scan_blocks / k_mesh_keep_offsets / k_mesh_keep_emit   iso.hip's stable compaction over the two flags
+//   scan.h's three (MeshKeepSrc) / k_mesh_keep_emit   stable compaction: the exclusive scan of the two flag arrays, then the copy
 // Nearest neighbour (exact; fp32 squared distance (dx dx + dy dy) + dz dz without contraction, ties to the smallest index):
 //   k_nn_bbox / k_nn_header     box of the finite points -> the grid (at most one cell per four finite points, at least one per axis)
-//   k_nn_count / k_mesh_scan_* / k_nn_fill   counting sort of the points by cell (z fastest) into (x, y, z, index) records
+//   k_nn_count / scan.h's three (NnSrc) / k_nn_fill   counting sort of the points by cell (z fastest) into (x, y, z, index) records
 //   k_nn_query           one thread per query: Chebyshev shells around the query's (clamped) cell until the stop rule proves the rest away
 //
 // Integer atomics, and why no result depends on their order: atomicMin on parent[] (a round's outcome may differ from call to call,
@@ -33,19 +33,11 @@
 
 namespace es {
 
-constexpr int MESH_PER_THREAD = 16;                          // consecutive items of one thread of the scan kernels
-constexpr int MESH_CHUNK = 256 * MESH_PER_THREAD;            // items per scan workgroup
 constexpr long long MESH_MAX = 1ll << 31;                    // int32 indices
-constexpr unsigned MESH_MAX_GRID = 1u << 16;                 // grid-stride launches
 constexpr int MESH_WALK = 32;                                // links one thread of k_mesh_jump follows
 constexpr int NN_PARTS = 1024;                               // workgroups of the bounding-box reduction
 constexpr int NN_PER_CELL = 4;                               // finite points per cell the grid aims for
 
-static inline long long mesh_up16(long long b) { return (b + 15) / 16 * 16; }
-static inline unsigned mesh_grid(long long n) {
-    const long long wg = (n + 255) / 256;
-    return (unsigned)(wg < 1 ? 1 : (wg < MESH_MAX_GRID ? wg : MESH_MAX_GRID));
-}
 static inline int mesh_jump_passes(long long V) {
     int bits = 0;
     while ((1ll << bits) < V) ++bits;                        // ceil(log2 V)
@@ -60,26 +52,21 @@ struct MeshScratch {
     int* boff;               // [nblk][2] exclusive scan of bsum
     unsigned char* vflag;    // [V] vertex survives the filter
     unsigned char* tflag;    // [T] triangle survives the filter
-    long long nblk;
+    long long nblk, bytes;
 };
-static inline long long mesh_nblk(long long V, long long T) {
-    const long long n = V > T ? V : T;
-    return n > 0 ? (n + MESH_CHUNK - 1) / MESH_CHUNK : 1;
-}
-static inline long long mesh_scratch_bytes(long long V, long long T) {
-    return 2 * mesh_up16(4 * V) + mesh_up16(4 * T) + 2 * mesh_up16(8 * mesh_nblk(V, T)) + mesh_up16(V) + mesh_up16(T) + 16;
-}
-static inline MeshScratch mesh_carve(void* scratch, long long V, long long T) {
+static MeshScratch mesh_layout(const void* scratch, long long V, long long T) {          // a null scratch measures only
+    Carver c(scratch);
     MeshScratch s;
-    s.nblk = mesh_nblk(V, T);
-    char* p = static_cast<char*>(scratch);
-    s.parent = reinterpret_cast<int*>(p); p += mesh_up16(4 * V);
-    s.voff = reinterpret_cast<int*>(p); p += mesh_up16(4 * V);
-    s.toff = reinterpret_cast<int*>(p); p += mesh_up16(4 * T);
-    s.bsum = reinterpret_cast<int*>(p); p += mesh_up16(8 * s.nblk);
-    s.boff = reinterpret_cast<int*>(p); p += mesh_up16(8 * s.nblk);
-    s.vflag = reinterpret_cast<unsigned char*>(p); p += mesh_up16(V);
-    s.tflag = reinterpret_cast<unsigned char*>(p);
+    s.nblk = V > 0 || T > 0 ? scan_chunks(V > T ? V : T) : 1;
+    s.parent = c.take<int>(V);
+    s.voff = c.take<int>(V);
+    s.toff = c.take<int>(T);
+    s.bsum = c.take<int>(2 * s.nblk);
+    s.boff = c.take<int>(2 * s.nblk);
+    s.vflag = c.take<unsigned char>(V);
+    s.tflag = c.take<unsigned char>(T);
+    c.take<char>(16);          // (unused: es_mesh_scratch_bytes has always counted it)
+    s.bytes = c.off;
     return s;
 }
 
@@ -196,69 +183,39 @@ __global__ __launch_bounds__(256) void k_mesh_keep_flags(const int* __restrict__
     }
 }
 
-// 16 consecutive flags of a thread (0 beyond n) -> how many are set
-__device__ __forceinline__ void flags_load(const unsigned char* __restrict__ f, long long n, long long i0, unsigned char (&c)[MESH_PER_THREAD]) {
-    if (i0 + MESH_PER_THREAD <= n) {
+// 16 consecutive flags of a thread (0 beyond n)
+__device__ __forceinline__ void flags_load(const unsigned char* __restrict__ f, long long n, long long i0, unsigned char (&c)[SCAN_PER_THREAD]) {
+    if (i0 + SCAN_PER_THREAD <= n) {
         const uint4 w = *reinterpret_cast<const uint4*>(f + i0);          // 16-byte aligned: f is, i0 a multiple of 16
         __builtin_memcpy(c, &w, sizeof(c));
     } else {
 #pragma unroll
-        for (int i = 0; i < MESH_PER_THREAD; ++i) c[i] = i0 + i < n ? f[i0 + i] : (unsigned char)0;
+        for (int i = 0; i < SCAN_PER_THREAD; ++i) c[i] = i0 + i < n ? f[i0 + i] : (unsigned char)0;
     }
 }
-__device__ __forceinline__ int flags_sum(const unsigned char (&c)[MESH_PER_THREAD]) {
-    int n = 0;
+// the scan's source: the two flag arrays, of different length -> voff[i], toff[i]
+struct MeshKeepSrc {
+    using sum_t = int;
+    struct items_t { unsigned char v[SCAN_PER_THREAD], t[SCAN_PER_THREAD]; };
+    const unsigned char *vflag, *tflag;
+    long long V, T;
+    int *voff, *toff;
+    __device__ __forceinline__ void load(long long i0, items_t& c, int& nv, int& nt) const {
+        flags_load(vflag, V, i0, c.v);
+        flags_load(tflag, T, i0, c.t);
+        nv = 0; nt = 0;
 #pragma unroll
-    for (int i = 0; i < MESH_PER_THREAD; ++i) n += c[i] ? 1 : 0;
-    return n;
-}
-
-__global__ __launch_bounds__(256) void k_mesh_keep_blocksum(const unsigned char* __restrict__ vflag, long long V, const unsigned char* __restrict__ tflag,
-                                                            long long T, int* __restrict__ bsum) {
-    __shared__ int part[4][2];
-    unsigned char cv[MESH_PER_THREAD], ct[MESH_PER_THREAD];
-    const long long i0 = (long long)blockIdx.x * MESH_CHUNK + threadIdx.x * MESH_PER_THREAD;
-    flags_load(vflag, V, i0, cv);
-    flags_load(tflag, T, i0, ct);
-    int nv = flags_sum(cv), nt = flags_sum(ct);
-    int total[2];
-    block_scan2(nv, nt, part, total);
-    if (threadIdx.x == 0) { bsum[2 * (size_t)blockIdx.x] = total[0]; bsum[2 * (size_t)blockIdx.x + 1] = total[1]; }
-}
-
-// iso.hip k_iso_scan_blocks: one workgroup, thread i owns a contiguous run of chunks; 64-bit sums, stored truncated
-__global__ __launch_bounds__(256) void k_mesh_scan_blocks(const int* __restrict__ bsum, long long nblk, int* __restrict__ boff, long long* __restrict__ totals) {
-    __shared__ long long part[4][2];
-    const long long per = (nblk + 255) / 256, b0 = threadIdx.x * per, b1 = b0 + per < nblk ? b0 + per : nblk;
-    long long sv = 0, st = 0;
-    for (long long b = b0; b < b1; ++b) { sv += bsum[2 * b]; st += bsum[2 * b + 1]; }
-    long long total[2];
-    block_scan2(sv, st, part, total);
-    for (long long b = b0; b < b1; ++b) {
-        boff[2 * b] = (int)sv; boff[2 * b + 1] = (int)st;
-        sv += bsum[2 * b]; st += bsum[2 * b + 1];
+        for (int i = 0; i < SCAN_PER_THREAD; ++i) { nv += c.v[i] ? 1 : 0; nt += c.t[i] ? 1 : 0; }
     }
-    if (threadIdx.x == 0 && totals) { totals[0] = total[0]; totals[1] = total[1]; }
-}
-
-__global__ __launch_bounds__(256) void k_mesh_keep_offsets(const unsigned char* __restrict__ vflag, long long V, const unsigned char* __restrict__ tflag,
-                                                           long long T, const int* __restrict__ boff, int* __restrict__ voff, int* __restrict__ toff) {
-    __shared__ int part[4][2];
-    unsigned char cv[MESH_PER_THREAD], ct[MESH_PER_THREAD];
-    const long long i0 = (long long)blockIdx.x * MESH_CHUNK + threadIdx.x * MESH_PER_THREAD;
-    flags_load(vflag, V, i0, cv);
-    flags_load(tflag, T, i0, ct);
-    int nv = flags_sum(cv), nt = flags_sum(ct);
-    int total[2];
-    block_scan2(nv, nt, part, total);
-    nv += boff[2 * (size_t)blockIdx.x]; nt += boff[2 * (size_t)blockIdx.x + 1];
+    __device__ __forceinline__ void store(long long i0, const items_t& c, int nv, int nt) const {
 #pragma unroll
-    for (int i = 0; i < MESH_PER_THREAD; ++i) {
-        if (i0 + i < V) voff[i0 + i] = nv;
-        if (i0 + i < T) toff[i0 + i] = nt;
-        nv += cv[i] ? 1 : 0; nt += ct[i] ? 1 : 0;
+        for (int i = 0; i < SCAN_PER_THREAD; ++i) {
+            if (i0 + i < V) voff[i0 + i] = nv;
+            if (i0 + i < T) toff[i0 + i] = nt;
+            nv += c.v[i] ? 1 : 0; nt += c.t[i] ? 1 : 0;
+        }
     }
-}
+};
 
 // Every write is checked against the capacity of its output buffer, every index against V.
 __global__ __launch_bounds__(256) void k_mesh_keep_emit(const float* __restrict__ verts, const int* __restrict__ tris, int V, long long T,
@@ -311,25 +268,24 @@ struct NnScratch {
     int* bsum;               // [nblk][2]
     int* boff;               // [nblk][2]
     float4* rec;             // [P] (x, y, z, index) sorted by cell
-    long long nblk;
+    long long nblk, bytes;
 };
-static inline long long nn_scratch_bytes(long long P) {
-    const long long nblk = (P + 1 + MESH_CHUNK - 1) / MESH_CHUNK;
-    return 64 + mesh_up16(32ll * NN_PARTS) + mesh_up16(4 * P) + 3 * mesh_up16(4 * (P + 1)) + 2 * mesh_up16(8 * nblk) + 16 * P + 16;
-}
-static inline NnScratch nn_carve(void* scratch, long long P) {
+static_assert(sizeof(NnHeader) == 64, "the header's region");
+static NnScratch nn_layout(const void* scratch, long long P) {          // a null scratch measures only
+    Carver c(scratch);
     NnScratch s;
-    s.nblk = (P + 1 + MESH_CHUNK - 1) / MESH_CHUNK;
-    char* p = static_cast<char*>(scratch);
-    s.head = reinterpret_cast<NnHeader*>(p); p += 64;
-    s.part = reinterpret_cast<float*>(p); p += mesh_up16(32ll * NN_PARTS);
-    s.cell = reinterpret_cast<int*>(p); p += mesh_up16(4 * P);
-    s.count = reinterpret_cast<int*>(p); p += mesh_up16(4 * (P + 1));
-    s.cursor = reinterpret_cast<int*>(p); p += mesh_up16(4 * (P + 1));
-    s.start = reinterpret_cast<int*>(p); p += mesh_up16(4 * (P + 1));
-    s.bsum = reinterpret_cast<int*>(p); p += mesh_up16(8 * s.nblk);
-    s.boff = reinterpret_cast<int*>(p); p += mesh_up16(8 * s.nblk);
-    s.rec = reinterpret_cast<float4*>(p);
+    s.nblk = scan_chunks(P + 1);
+    s.head = c.take<NnHeader>(1);
+    s.part = c.take<float>(8ll * NN_PARTS);
+    s.cell = c.take<int>(P);
+    s.count = c.take<int>(P + 1);
+    s.cursor = c.take<int>(P + 1);          // (behind count: es_nn_build zeroes both with one memset)
+    s.start = c.take<int>(P + 1);
+    s.bsum = c.take<int>(2 * s.nblk);
+    s.boff = c.take<int>(2 * s.nblk);
+    s.rec = c.take<float4>(P);
+    c.take<char>(16);          // (unused: es_nn_scratch_bytes has always counted it)
+    s.bytes = c.off;
     return s;
 }
 
@@ -463,39 +419,26 @@ __global__ __launch_bounds__(256) void k_nn_count(const float* __restrict__ pts,
     }
 }
 
-// exclusive scan of count[0 .. n) in iso.hip's three launches (second sequence unused)
-__device__ __forceinline__ void ints_load(const int* __restrict__ f, long long n, long long i0, int (&c)[MESH_PER_THREAD]) {
+// the scan's source: count[0 .. n) -> start[] (one sequence; the second stays 0)
+struct NnSrc {
+    using sum_t = int;
+    using items_t = int[SCAN_PER_THREAD];
+    const int* count;
+    long long n;
+    int* start;
+    __device__ __forceinline__ void load(long long i0, items_t& c, int& s, int& none) const {
+        s = 0; none = 0;
 #pragma unroll
-    for (int i = 0; i < MESH_PER_THREAD; ++i) c[i] = i0 + i < n ? f[i0 + i] : 0;
-}
-__global__ __launch_bounds__(256) void k_nn_blocksum(const int* __restrict__ count, long long n, int* __restrict__ bsum) {
-    __shared__ int part[4][2];
-    int c[MESH_PER_THREAD];
-    ints_load(count, n, (long long)blockIdx.x * MESH_CHUNK + threadIdx.x * MESH_PER_THREAD, c);
-    int s = 0, z = 0;
-#pragma unroll
-    for (int i = 0; i < MESH_PER_THREAD; ++i) s += c[i];
-    int total[2];
-    block_scan2(s, z, part, total);
-    if (threadIdx.x == 0) { bsum[2 * (size_t)blockIdx.x] = total[0]; bsum[2 * (size_t)blockIdx.x + 1] = 0; }
-}
-__global__ __launch_bounds__(256) void k_nn_offsets(const int* __restrict__ count, long long n, const int* __restrict__ boff, int* __restrict__ start) {
-    __shared__ int part[4][2];
-    int c[MESH_PER_THREAD];
-    const long long i0 = (long long)blockIdx.x * MESH_CHUNK + threadIdx.x * MESH_PER_THREAD;
-    ints_load(count, n, i0, c);
-    int s = 0, z = 0;
-#pragma unroll
-    for (int i = 0; i < MESH_PER_THREAD; ++i) s += c[i];
-    int total[2];
-    block_scan2(s, z, part, total);
-    s += boff[2 * (size_t)blockIdx.x];
-#pragma unroll
-    for (int i = 0; i < MESH_PER_THREAD; ++i) {
-        if (i0 + i < n) start[i0 + i] = s;
-        s += c[i];
+        for (int i = 0; i < SCAN_PER_THREAD; ++i) { c[i] = i0 + i < n ? count[i0 + i] : 0; s += c[i]; }
     }
-}
+    __device__ __forceinline__ void store(long long i0, const items_t& c, int s, int) const {
+#pragma unroll
+        for (int i = 0; i < SCAN_PER_THREAD; ++i) {
+            if (i0 + i < n) start[i0 + i] = s;
+            s += c[i];
+        }
+    }
+};
 
 __global__ __launch_bounds__(256) void k_nn_fill(const float* __restrict__ pts, long long P, const int* __restrict__ cell, const int* __restrict__ start,
                                                  int* cursor, float4* __restrict__ rec) {
@@ -611,37 +554,34 @@ static int nn_check(long long P, long long Q) {
 
 using namespace es;
 
-#define MESH_SCRATCH_OK(scratch) \
-    ES_REQUIRE(scratch && reinterpret_cast<uintptr_t>(scratch) % 16 == 0, "mesh scratch must be a 16-byte aligned device buffer")
-
 extern "C" {
 
 int64_t es_mesh_scratch_bytes(long long n_verts, long long n_tris) {
     if (mesh_check(n_verts, n_tris) != ST_OK) return -1;
-    return mesh_scratch_bytes(n_verts, n_tris);
+    return mesh_layout(nullptr, n_verts, n_tris).bytes;
 }
 
 int es_mesh_cc_begin(const int* tris, long long V, long long T, void* scratch, void* stream) {
     if (const int s = mesh_check(V, T)) return s;
     ES_REQUIRE(tris || T == 0, "es_mesh_cc_begin needs tris");
-    MESH_SCRATCH_OK(scratch);
+    ES_SCRATCH_OK(scratch, "mesh scratch");
     if (V == 0) return ST_OK;
-    const MeshScratch s = mesh_carve(scratch, V, T);
-    hipLaunchKernelGGL(k_mesh_init, dim3(mesh_grid(V)), dim3(256), 0, static_cast<hipStream_t>(stream), s.parent, (int)V);
+    const MeshScratch s = mesh_layout(scratch, V, T);
+    hipLaunchKernelGGL(k_mesh_init, dim3(grid_for(V)), dim3(256), 0, static_cast<hipStream_t>(stream), s.parent, (int)V);
     return hip_last("es_mesh_cc_begin");
 }
 
 int es_mesh_cc_round(const int* tris, long long V, long long T, void* scratch, int* changed, void* stream) {
     if (const int s = mesh_check(V, T)) return s;
     ES_REQUIRE((tris || T == 0) && changed, "es_mesh_cc_round needs tris and changed");
-    MESH_SCRATCH_OK(scratch);
+    ES_SCRATCH_OK(scratch, "mesh scratch");
     hipStream_t st = static_cast<hipStream_t>(stream);
     ES_HIP(hipMemsetAsync(changed, 0, sizeof(int), st));
     if (V == 0 || T == 0) return ST_OK;
-    const MeshScratch s = mesh_carve(scratch, V, T);
-    hipLaunchKernelGGL(k_mesh_hook, dim3(mesh_grid(T)), dim3(256), 0, st, tris, (int)V, T, s.parent, changed);
+    const MeshScratch s = mesh_layout(scratch, V, T);
+    hipLaunchKernelGGL(k_mesh_hook, dim3(grid_for(T)), dim3(256), 0, st, tris, (int)V, T, s.parent, changed);
     for (int pass = 0, n = mesh_jump_passes(V); pass < n; ++pass)
-        hipLaunchKernelGGL(k_mesh_jump, dim3(mesh_grid(V)), dim3(256), 0, st, s.parent, (int)V);
+        hipLaunchKernelGGL(k_mesh_jump, dim3(grid_for(V)), dim3(256), 0, st, s.parent, (int)V);
     return hip_last("es_mesh_cc_round");
 }
 
@@ -651,9 +591,9 @@ int es_mesh_cc_finish(const int* tris, long long V, long long T, const void* scr
     ES_REQUIRE((tris || T == 0) && totals, "es_mesh_cc_finish needs tris and totals");
     ES_REQUIRE((V == 0 || (vertex_label && component_triangles)) && (T == 0 || triangle_label),
                "es_mesh_cc_finish needs vertex_label, triangle_label and component_triangles");
-    MESH_SCRATCH_OK(scratch);
+    ES_SCRATCH_OK(scratch, "mesh scratch");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const MeshScratch s = mesh_carve(const_cast<void*>(scratch), V, T);
+    const MeshScratch s = mesh_layout(scratch, V, T);
     ES_HIP(hipMemsetAsync(totals, 0, 3 * sizeof(long long), st));
     if (V > 0) {
         ES_HIP(hipMemcpyAsync(vertex_label, s.parent, 4 * V, hipMemcpyDeviceToDevice, st));
@@ -661,8 +601,8 @@ int es_mesh_cc_finish(const int* tris, long long V, long long T, const void* scr
     }
     unsigned long long* tot = reinterpret_cast<unsigned long long*>(totals);
     if (T > 0)
-        hipLaunchKernelGGL(k_mesh_label, dim3(mesh_grid(T)), dim3(256), 0, st, tris, (int)V, T, s.parent, triangle_label, component_triangles, tot);
-    if (V > 0) hipLaunchKernelGGL(k_mesh_stats, dim3(mesh_grid(V)), dim3(256), 0, st, component_triangles, (int)V, tot);
+        hipLaunchKernelGGL(k_mesh_label, dim3(grid_for(T)), dim3(256), 0, st, tris, (int)V, T, s.parent, triangle_label, component_triangles, tot);
+    if (V > 0) hipLaunchKernelGGL(k_mesh_stats, dim3(grid_for(V)), dim3(256), 0, st, component_triangles, (int)V, tot);
     return hip_last("es_mesh_cc_finish");
 }
 
@@ -673,16 +613,14 @@ int es_mesh_keep_count(const int* tris, long long V, long long T, const int* tri
     ES_REQUIRE(max_triangles >= 0 && max_triangles <= T, "es_mesh_keep_count: max_triangles outside 0..T");
     ES_REQUIRE(totals && (T == 0 || (tris && triangle_label && component_triangles)),
                "es_mesh_keep_count needs tris, triangle_label, component_triangles and totals");
-    MESH_SCRATCH_OK(scratch);
+    ES_SCRATCH_OK(scratch, "mesh scratch");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const MeshScratch s = mesh_carve(scratch, V, T);
+    const MeshScratch s = mesh_layout(scratch, V, T);
     if (V > 0) ES_HIP(hipMemsetAsync(s.vflag, compact ? 0 : 1, V, st));
     if (T > 0)
-        hipLaunchKernelGGL(k_mesh_keep_flags, dim3(mesh_grid(T)), dim3(256), 0, st, tris, (int)V, T, triangle_label, component_triangles,
+        hipLaunchKernelGGL(k_mesh_keep_flags, dim3(grid_for(T)), dim3(256), 0, st, tris, (int)V, T, triangle_label, component_triangles,
                            keep_ratio * (double)max_triangles, compact, s.tflag, s.vflag);
-    hipLaunchKernelGGL(k_mesh_keep_blocksum, dim3((unsigned)s.nblk), dim3(256), 0, st, s.vflag, V, s.tflag, T, s.bsum);
-    hipLaunchKernelGGL(k_mesh_scan_blocks, dim3(1), dim3(256), 0, st, s.bsum, s.nblk, s.boff, totals);
-    hipLaunchKernelGGL(k_mesh_keep_offsets, dim3((unsigned)s.nblk), dim3(256), 0, st, s.vflag, V, s.tflag, T, s.boff, s.voff, s.toff);
+    scan_launch(MeshKeepSrc{s.vflag, s.tflag, V, T, s.voff, s.toff}, s.nblk, s.bsum, s.boff, totals, st);
     return hip_last("es_mesh_keep_count");
 }
 
@@ -690,36 +628,34 @@ int es_mesh_keep_emit(const float* verts, const int* tris, long long V, long lon
                       int* tris_out, long long* vertex_map, void* stream) {
     if (const int s = mesh_check(V, T)) return s;
     ES_REQUIRE(V2 >= 0 && V2 <= V && T2 >= 0 && T2 <= T, "es_mesh_keep_emit: kept counts outside 0..V / 0..T");
-    MESH_SCRATCH_OK(scratch);
+    ES_SCRATCH_OK(scratch, "mesh scratch");
     if (V2 == 0 && T2 == 0) return ST_OK;
     ES_REQUIRE((T2 == 0 || (tris && tris_out)) && (!verts_out || verts), "es_mesh_keep_emit needs tris, tris_out and verts for verts_out");
-    const MeshScratch s = mesh_carve(const_cast<void*>(scratch), V, T);
-    hipLaunchKernelGGL(k_mesh_keep_emit, dim3(mesh_grid(V > T ? V : T)), dim3(256), 0, static_cast<hipStream_t>(stream), verts, tris, (int)V, T, s.voff,
+    const MeshScratch s = mesh_layout(scratch, V, T);
+    hipLaunchKernelGGL(k_mesh_keep_emit, dim3(grid_for(V > T ? V : T)), dim3(256), 0, static_cast<hipStream_t>(stream), verts, tris, (int)V, T, s.voff,
                        s.toff, s.vflag, s.tflag, (int)V2, (int)T2, verts_out, tris_out, vertex_map);
     return hip_last("es_mesh_keep_emit");
 }
 
 int64_t es_nn_scratch_bytes(long long n_points) {
     if (nn_check(n_points, 0) != ST_OK) return -1;
-    return nn_scratch_bytes(n_points);
+    return nn_layout(nullptr, n_points).bytes;
 }
 
 int es_nn_build(const float* points, long long P, void* scratch, void* stream) {
     if (const int s = nn_check(P, 0)) return s;
     ES_REQUIRE(points || P == 0, "es_nn_build needs points");
-    MESH_SCRATCH_OK(scratch);
+    ES_SCRATCH_OK(scratch, "mesh scratch");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const NnScratch s = nn_carve(scratch, P);
-    const int nparts = (int)(mesh_grid(P) < (unsigned)NN_PARTS ? mesh_grid(P) : (unsigned)NN_PARTS);
+    const NnScratch s = nn_layout(scratch, P);
+    const int nparts = (int)(grid_for(P) < (unsigned)NN_PARTS ? grid_for(P) : (unsigned)NN_PARTS);
     ES_HIP(hipMemsetAsync(s.count, 0, reinterpret_cast<char*>(s.start) - reinterpret_cast<char*>(s.count), st));          // count and cursor
     hipLaunchKernelGGL(k_nn_bbox, dim3(nparts), dim3(256), 0, st, points, P, s.part);
     hipLaunchKernelGGL(k_nn_header, dim3(1), dim3(256), 0, st, s.part, nparts, s.head);
     if (P == 0) return hip_last("es_nn_build");
-    hipLaunchKernelGGL(k_nn_count, dim3(mesh_grid(P)), dim3(256), 0, st, points, P, s.head, s.cell, s.count);
-    hipLaunchKernelGGL(k_nn_blocksum, dim3((unsigned)s.nblk), dim3(256), 0, st, s.count, P + 1, s.bsum);
-    hipLaunchKernelGGL(k_mesh_scan_blocks, dim3(1), dim3(256), 0, st, s.bsum, s.nblk, s.boff, static_cast<long long*>(nullptr));
-    hipLaunchKernelGGL(k_nn_offsets, dim3((unsigned)s.nblk), dim3(256), 0, st, s.count, P + 1, s.boff, s.start);
-    hipLaunchKernelGGL(k_nn_fill, dim3(mesh_grid(P)), dim3(256), 0, st, points, P, s.cell, s.start, s.cursor, s.rec);
+    hipLaunchKernelGGL(k_nn_count, dim3(grid_for(P)), dim3(256), 0, st, points, P, s.head, s.cell, s.count);
+    scan_launch(NnSrc{s.count, P + 1, s.start}, s.nblk, s.bsum, s.boff, nullptr, st);
+    hipLaunchKernelGGL(k_nn_fill, dim3(grid_for(P)), dim3(256), 0, st, points, P, s.cell, s.start, s.cursor, s.rec);
     return hip_last("es_nn_build");
 }
 
@@ -727,9 +663,9 @@ int es_nn_query(const float* query, long long Q, long long P, const void* scratc
     if (const int s = nn_check(P, Q)) return s;
     if (Q == 0) return ST_OK;
     ES_REQUIRE(query && dist && index, "es_nn_query needs query, dist and index");
-    MESH_SCRATCH_OK(scratch);
-    const NnScratch s = nn_carve(const_cast<void*>(scratch), P);
-    hipLaunchKernelGGL(k_nn_query, dim3(mesh_grid(Q)), dim3(256), 0, static_cast<hipStream_t>(stream), query, Q, P, s.head, s.start, s.rec, dist, index);
+    ES_SCRATCH_OK(scratch, "mesh scratch");
+    const NnScratch s = nn_layout(scratch, P);
+    hipLaunchKernelGGL(k_nn_query, dim3(grid_for(Q)), dim3(256), 0, static_cast<hipStream_t>(stream), query, Q, P, s.head, s.start, s.rec, dist, index);
     return hip_last("es_nn_query");
 }
 

@@ -46,7 +46,6 @@ constexpr int EVAL_MAX_C = 16;                               // channels of es_m
 constexpr long long EVAL_MAX_COUNT = 1ll << 31;              // every element count stays inside int32
 constexpr int SQ_PER_THREAD = 8;
 constexpr int SQ_CHUNK = 256 * SQ_PER_THREAD;                // pixels per workgroup of k_masked_sq_sums
-constexpr unsigned EVAL_MAX_GRID = 1u << 16;                 // grid-stride launches of the panel kernels
 
 static inline int ssim_tiles_x(int W) { return (W - SSIM_K + 1 + SSIM_TILE - 1) / SSIM_TILE; }
 static inline int ssim_tiles_y(int H) { return (H - SSIM_K + 1 + SSIM_TILE - 1) / SSIM_TILE; }
@@ -254,10 +253,6 @@ static int panel_out(int n, int H, int W, unsigned char* out, long long pitch, i
     o.out = out; o.pitch = pitch; o.col = col;
     return ST_OK;
 }
-static inline unsigned eval_grid(long long items) {
-    const long long wg = (items + 255) / 256;
-    return (unsigned)(wg < 1 ? 1 : (wg < EVAL_MAX_GRID ? wg : EVAL_MAX_GRID));
-}
 
 }  // namespace es
 
@@ -322,7 +317,7 @@ int es_eval_panel_rgb(const float* x, int n, int height, int width, int channels
     if (n == 0) return ST_OK;
     ES_REQUIRE(x, "es_eval_panel_rgb needs its image");
     const long long pixels = (long long)n * height * width;
-    hipLaunchKernelGGL(k_panel_rgb, dim3(eval_grid(pixels)), dim3(256), 0, static_cast<hipStream_t>(stream), x, pixels, height, width, channels, o);
+    hipLaunchKernelGGL(k_panel_rgb, dim3(grid_for(pixels)), dim3(256), 0, static_cast<hipStream_t>(stream), x, pixels, height, width, channels, o);
     return hip_last("es_eval_panel_rgb");
 }
 
@@ -333,7 +328,7 @@ int es_eval_panel_depth(const float* depth, int n, int height, int width, double
     if (n == 0) return ST_OK;
     ES_REQUIRE(depth, "es_eval_panel_depth needs its image");
     const long long pixels = (long long)n * height * width;
-    hipLaunchKernelGGL(k_panel_depth, dim3(eval_grid(pixels)), dim3(256), 0, static_cast<hipStream_t>(stream), depth, pixels, height, width, depth_max, o);
+    hipLaunchKernelGGL(k_panel_depth, dim3(grid_for(pixels)), dim3(256), 0, static_cast<hipStream_t>(stream), depth, pixels, height, width, depth_max, o);
     return hip_last("es_eval_panel_depth");
 }
 
@@ -344,7 +339,7 @@ int es_eval_panel_normal(const float* normals, const float* rot, int n, int heig
     if (n == 0) return ST_OK;
     ES_REQUIRE(normals && rot, "es_eval_panel_normal needs normals and one 3 x 3 rotation per frame");
     const long long pixels = (long long)n * height * width;
-    hipLaunchKernelGGL(k_panel_normal, dim3(eval_grid(pixels)), dim3(256), 0, static_cast<hipStream_t>(stream), normals, rot, pixels, height, width,
+    hipLaunchKernelGGL(k_panel_normal, dim3(grid_for(pixels)), dim3(256), 0, static_cast<hipStream_t>(stream), normals, rot, pixels, height, width,
                        revert != 0, out_f, o);
     return hip_last("es_eval_panel_normal");
 }

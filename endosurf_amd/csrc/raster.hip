@@ -9,7 +9,8 @@
 //   k_rast_setup        one thread per triangle: the rejection tests, the pixel box clamped to the image -> count[t] = the number of
 //                       8 x 8-pixel tiles the box touches, or -reason for a rejected triangle
 //   k_rast_blocksum / k_rast_scan_blocks / k_rast_offsets
-//                       iso.hip's three-launch exclusive scan over count -> offset[t], totals = {work items, rejected by reason}
+//                       the three-launch exclusive scan of scan.h over count -> offset[t], totals = {work items, rejected by reason}.
+//                       Kernels of raster's own: one sequence is scanned, the five reasons are only summed in the same launches
 //   k_rast_fill         one thread per work item (its triangle by binary search in offset): the at most 64 pixel centres of box and
 //                       tile; coverage by three int64 edge functions with a top-left rule for the value 0; depth from fp64
 //                       barycentrics of the exact integers; one atomicMin of (bits of float32(z) << 32 | t) on zbuf[i W + j]
@@ -40,10 +41,7 @@ constexpr int RAST_SUB = 256;                                // fixed-point unit
 constexpr int RAST_GUARD = 1 << 22;                          // |fixed-point coordinate| <= this
 constexpr int RAST_MAX_SIZE = 8192;                          // largest image side
 constexpr int RAST_MAX_ATTRS = 8;
-constexpr int RAST_PER_THREAD = 16;                          // consecutive triangles of one thread of the scan kernels
-constexpr int RAST_CHUNK = 256 * RAST_PER_THREAD;            // triangles per scan workgroup
 constexpr long long RAST_MAX_COUNT = 1ll << 31;              // int32 indices
-constexpr unsigned RAST_MAX_GRID = 1u << 16;                 // grid-stride launches
 constexpr unsigned long long RAST_EMPTY = ~0ull;             // the key of a pixel nothing covers
 constexpr int RAST_TOTALS = 8;                               // work items, invalid, near, zero area, culled, off screen, covered pixels, 0
 enum { RAST_INVALID = 1, RAST_NEAR = 2, RAST_AREA = 3, RAST_CULLED = 4, RAST_OFFSCREEN = 5 };
@@ -65,25 +63,20 @@ struct RastScratch {
     long long* boff;                 // [nchunk] exclusive scan of the work items
     int* cov;                        // [ncov] covered pixels per workgroup of k_rast_resolve
     int nchunk, ncov;
+    long long bytes;
 };
-static inline long long rast_up16(long long b) { return (b + 15) / 16 * 16; }
-static inline int rast_nchunk(long long T) { return (int)((T + RAST_CHUNK - 1) / RAST_CHUNK); }
-static inline int rast_ncov(int H, int W) { return (int)(((long long)H * W + 255) / 256); }
-static inline long long rast_scratch_bytes(long long T, int H, int W) {
-    return rast_up16(8ll * H * W) + 2 * rast_up16(4 * T) + rast_up16(48ll * rast_nchunk(T)) + rast_up16(8ll * rast_nchunk(T)) +
-           rast_up16(4ll * rast_ncov(H, W));
-}
-static inline RastScratch rast_carve(void* scratch, long long T, int H, int W) {
+static RastScratch rast_layout(const void* scratch, long long T, int H, int W) {          // a null scratch measures only
+    Carver c(scratch);
     RastScratch s;
-    s.nchunk = rast_nchunk(T);
-    s.ncov = rast_ncov(H, W);
-    char* p = static_cast<char*>(scratch);
-    s.zbuf = reinterpret_cast<unsigned long long*>(p); p += rast_up16(8ll * H * W);
-    s.count = reinterpret_cast<int*>(p); p += rast_up16(4 * T);
-    s.offset = reinterpret_cast<int*>(p); p += rast_up16(4 * T);
-    s.bsum = reinterpret_cast<long long*>(p); p += rast_up16(48ll * s.nchunk);
-    s.boff = reinterpret_cast<long long*>(p); p += rast_up16(8ll * s.nchunk);
-    s.cov = reinterpret_cast<int*>(p);
+    s.nchunk = (int)scan_chunks(T);
+    s.ncov = (int)(((long long)H * W + 255) / 256);
+    s.zbuf = c.take<unsigned long long>((long long)H * W);
+    s.count = c.take<int>(T);
+    s.offset = c.take<int>(T);
+    s.bsum = c.take<long long>(6ll * s.nchunk);
+    s.boff = c.take<long long>(s.nchunk);
+    s.cov = c.take<int>(s.ncov);
+    s.bytes = c.off;
     return s;
 }
 
@@ -190,7 +183,7 @@ __device__ __forceinline__ void rast_chunk_counts(const int* __restrict__ count,
 #pragma unroll
     for (int k = 0; k < 6; ++k) v[k] = 0;
 #pragma unroll
-    for (int i = 0; i < RAST_PER_THREAD; ++i) {
+    for (int i = 0; i < SCAN_PER_THREAD; ++i) {
         const int t = t0 + i;
         if (t >= T) continue;
         const int c = count[t];
@@ -203,7 +196,7 @@ __device__ __forceinline__ void rast_chunk_counts(const int* __restrict__ count,
 __global__ __launch_bounds__(256) void k_rast_blocksum(const int* __restrict__ count, int T, long long* __restrict__ bsum) {
     __shared__ long long part[4][2];
     long long v[6], total[2];
-    rast_chunk_counts(count, T, blockIdx.x * RAST_CHUNK + threadIdx.x * RAST_PER_THREAD, v);
+    rast_chunk_counts(count, T, blockIdx.x * SCAN_CHUNK + threadIdx.x * SCAN_PER_THREAD, v);
 #pragma unroll
     for (int k = 0; k < 6; k += 2) {
         block_scan2(v[k], v[k + 1], part, total);
@@ -211,7 +204,7 @@ __global__ __launch_bounds__(256) void k_rast_blocksum(const int* __restrict__ c
     }
 }
 
-// One workgroup: thread i owns a contiguous run of chunks (iso.hip k_iso_scan_blocks).
+// One workgroup: thread i owns a contiguous run of chunks.
 __global__ __launch_bounds__(256) void k_rast_scan_blocks(const long long* __restrict__ bsum, int nchunk, long long* __restrict__ boff,
                                                           long long* __restrict__ totals) {
     __shared__ long long part[4][2];
@@ -233,13 +226,13 @@ __global__ __launch_bounds__(256) void k_rast_scan_blocks(const long long* __res
 
 __global__ __launch_bounds__(256) void k_rast_offsets(const int* __restrict__ count, int T, const long long* __restrict__ boff, int* __restrict__ offset) {
     __shared__ long long part[4][2];
-    const int t0 = blockIdx.x * RAST_CHUNK + threadIdx.x * RAST_PER_THREAD;
+    const int t0 = blockIdx.x * SCAN_CHUNK + threadIdx.x * SCAN_PER_THREAD;
     long long v[6], total[2], none = 0;
     rast_chunk_counts(count, T, t0, v);
     block_scan2(v[0], none, part, total);
     long long run = v[0] + boff[blockIdx.x];
 #pragma unroll
-    for (int i = 0; i < RAST_PER_THREAD; ++i) {
+    for (int i = 0; i < SCAN_PER_THREAD; ++i) {
         const int t = t0 + i;
         if (t >= T) continue;
         offset[t] = (int)run;          // (below 2^31 whenever the host goes on to k_rast_fill)
@@ -336,23 +329,16 @@ static int rast_view(long long V, long long T, int H, int W, double near, int cu
     g.V = (int)V; g.T = (int)T; g.H = H; g.W = W; g.cull = cull; g.near = near;
     return ST_OK;
 }
-static inline unsigned rast_grid(long long n) {
-    const long long wg = (n + 255) / 256;
-    return (unsigned)(wg < 1 ? 1 : (wg < RAST_MAX_GRID ? wg : RAST_MAX_GRID));
-}
 
 }  // namespace es
 
 using namespace es;
 
-#define RAST_SCRATCH_OK(scratch) \
-    ES_REQUIRE(scratch && reinterpret_cast<uintptr_t>(scratch) % 16 == 0, "raster scratch must be a 16-byte aligned device buffer")
-
 extern "C" {
 
 int64_t es_rast_scratch_bytes(long long n_verts, long long n_tris, int height, int width) {
     if (rast_check(n_verts, n_tris, height, width) != ST_OK) return -1;
-    return rast_scratch_bytes(n_tris, height, width);
+    return rast_layout(nullptr, n_tris, height, width).bytes;
 }
 
 int es_rast_project(const float* verts, long long V, const double* camera, int* xy, float* zc, void* stream) {
@@ -367,7 +353,7 @@ int es_rast_project(const float* verts, long long V, const double* camera, int* 
     ES_REQUIRE(c.k00 > 0.0 && c.k11 > 0.0, "focal lengths must be positive");
     if (V == 0) return ST_OK;
     ES_REQUIRE(verts && xy && zc, "es_rast_project needs verts, xy and zc");
-    hipLaunchKernelGGL(k_rast_project, dim3(rast_grid(V)), dim3(256), 0, static_cast<hipStream_t>(stream), verts, (int)V, c, xy, zc);
+    hipLaunchKernelGGL(k_rast_project, dim3(grid_for(V)), dim3(256), 0, static_cast<hipStream_t>(stream), verts, (int)V, c, xy, zc);
     return hip_last("es_rast_project");
 }
 
@@ -378,15 +364,15 @@ int es_rast_count(const int* tris, long long V, long long T, const int* xy, cons
     ES_REQUIRE(totals, "es_rast_count needs totals");
     ES_REQUIRE(T == 0 || tris, "es_rast_count needs tris");
     ES_REQUIRE(V == 0 || (xy && zc), "es_rast_count needs xy and zc");
-    RAST_SCRATCH_OK(scratch);
-    const RastScratch s = rast_carve(scratch, T, height, width);
+    ES_SCRATCH_OK(scratch, "raster scratch");
+    const RastScratch s = rast_layout(scratch, T, height, width);
     hipStream_t st = static_cast<hipStream_t>(stream);
     ES_HIP(hipMemsetAsync(s.zbuf, 0xFF, 8ull * height * width, st));
     if (T == 0) {
         ES_HIP(hipMemsetAsync(totals, 0, 8 * RAST_TOTALS, st));
         return ST_OK;
     }
-    hipLaunchKernelGGL(k_rast_setup, dim3(rast_grid(T)), dim3(256), 0, st, tris, xy, zc, g, s.count);
+    hipLaunchKernelGGL(k_rast_setup, dim3(grid_for(T)), dim3(256), 0, st, tris, xy, zc, g, s.count);
     hipLaunchKernelGGL(k_rast_blocksum, dim3((unsigned)s.nchunk), dim3(256), 0, st, s.count, g.T, s.bsum);
     hipLaunchKernelGGL(k_rast_scan_blocks, dim3(1), dim3(256), 0, st, s.bsum, s.nchunk, s.boff, totals);
     hipLaunchKernelGGL(k_rast_offsets, dim3((unsigned)s.nchunk), dim3(256), 0, st, s.count, g.T, s.boff, s.offset);
@@ -401,9 +387,9 @@ int es_rast_fill(const int* tris, long long V, long long T, const int* xy, const
     ES_REQUIRE(n_work < RAST_MAX_COUNT, "2^31 work items or more: too many large triangles for one call");
     if (n_work == 0 || T == 0) return ST_OK;
     ES_REQUIRE(tris && xy && zc, "es_rast_fill needs tris, xy and zc");
-    RAST_SCRATCH_OK(scratch);
-    const RastScratch s = rast_carve(scratch, T, height, width);
-    hipLaunchKernelGGL(k_rast_fill, dim3(rast_grid(n_work)), dim3(256), 0, static_cast<hipStream_t>(stream), tris, xy, zc, g, s.offset, n_work, s.zbuf);
+    ES_SCRATCH_OK(scratch, "raster scratch");
+    const RastScratch s = rast_layout(scratch, T, height, width);
+    hipLaunchKernelGGL(k_rast_fill, dim3(grid_for(n_work)), dim3(256), 0, static_cast<hipStream_t>(stream), tris, xy, zc, g, s.offset, n_work, s.zbuf);
     return hip_last("es_rast_fill");
 }
 
@@ -417,8 +403,8 @@ int es_rast_resolve(const int* tris, long long V, long long T, const int* xy, co
     ES_REQUIRE(n_attrs == 0 || attr_out, "es_rast_resolve needs attr_out");
     ES_REQUIRE(T == 0 || (tris && (V == 0 || (xy && zc))), "es_rast_resolve needs tris, xy and zc");
     ES_REQUIRE(n_attrs == 0 || V == 0 || T == 0 || attrs, "es_rast_resolve needs attrs");
-    RAST_SCRATCH_OK(scratch);
-    const RastScratch s = rast_carve(scratch, T, height, width);
+    ES_SCRATCH_OK(scratch, "raster scratch");
+    const RastScratch s = rast_layout(scratch, T, height, width);
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_rast_resolve, dim3((unsigned)s.ncov), dim3(256), 0, st, tris, xy, zc, attrs, n_attrs, g, s.zbuf, depth, triangle, bary,
                        attr_out, s.cov);

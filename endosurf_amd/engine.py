@@ -599,6 +599,30 @@ class Engine:
         check(self.lib.es_adam_step_dev(ptr(flat), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), n, beta1, beta2, eps, ptr(scalars_dev), ptr(grad_var),
                                         var_off, self.st()), "es_adam_step_dev")
 
+    # ---- argument and scratch helpers of the geometry and evaluation entry points -----------------------
+    def _scratch_bytes(self, fn_name, *dims):
+        """What ``es_*_scratch_bytes`` answers for ``dims``; its -1 (sizes the library refuses) raises with the library's message."""
+        nbytes = int(getattr(self.lib, fn_name)(*dims))
+        if nbytes < 0:
+            check(1, fn_name)
+        return nbytes
+
+    def _scratch(self, fn_name, *dims):
+        return self.empty(self._scratch_bytes(fn_name, *dims), dtype=torch.uint8)
+
+    def _tri_arg(self, tris, what):
+        """``tris`` as the library reads it: int32 [T, 3], contiguous, on this device."""
+        if tris.dim() != 2 or tris.shape[1] != 3 or tris.device != self.device or tris.dtype not in (torch.int32, torch.int64):
+            raise _lib.EndoSurfHipError(f"{what} takes [T, 3] int32 / int64 triangles on {self.device} (got {tris.dtype} {tuple(tris.shape)} "
+                                        f"on {tris.device})")
+        return tris.detach().to(torch.int32).contiguous()
+
+    def _rows3_arg(self, t, what, rows):
+        """``t`` ([N, 3] on this device; ``rows`` names it in the message) as the library reads it: fp32, contiguous."""
+        if t.dim() != 2 or t.shape[1] != 3 or t.device != self.device:
+            raise _lib.EndoSurfHipError(f"{what} takes {rows} on {self.device} (got {tuple(t.shape)} on {t.device})")
+        return f32(t)
+
     # ---- iso-surface extraction (csrc/iso.hip) -------------------------------------------------------
     def iso_surface(self, field: torch.Tensor, threshold: float = 0.0):
         """The level set ``field == threshold`` of a device field [nx, ny, nz] as a welded, oriented triangle mesh, triangulated like
@@ -608,10 +632,7 @@ class Engine:
             raise _lib.EndoSurfHipError(f"iso_surface takes a [nx, ny, nz] field on {self.device} (got {tuple(field.shape)} on {field.device})")
         u = f32(field)
         nx, ny, nz = (int(s) for s in u.shape)
-        nbytes = int(self.lib.es_iso_scratch_bytes(nx, ny, nz))
-        if nbytes < 0:
-            check(1, "es_iso_scratch_bytes")
-        scratch = self.empty(nbytes, dtype=torch.uint8)
+        scratch = self._scratch("es_iso_scratch_bytes", nx, ny, nz)
         totals = self.empty(2, dtype=torch.int64)
         check(self.lib.es_iso_count(ptr(u), nx, ny, nz, float(threshold), ptr(scratch), ptr(totals), self.st()), "es_iso_count")
         V, T = (int(v) for v in totals.tolist())
@@ -638,14 +659,11 @@ class Engine:
         ax = [f32(a) for a in axes]
         nx, ny, nz = (int(a.shape[0]) for a in ax)
         B, thr, chunk = int(block), float(threshold), max(1, int(net_chunk))
-        nbytes = int(self.lib.es_band_scratch_bytes(nx, ny, nz, B))
-        if nbytes < 0:
-            check(1, "es_band_scratch_bytes")
+        scratch = self._scratch("es_band_scratch_bytes", nx, ny, nz, B)
         nb = [-(-(n - 1) // B) for n in (nx, ny, nz)]
         NB, N, Nc = nb[0] * nb[1] * nb[2], nx * ny * nz, (nb[0] + 1) * (nb[1] + 1) * (nb[2] + 1)
         ends = torch.stack([torch.stack([a[0], a[-1]]) for a in ax]).tolist()          # (one small read: the world size of a block)
         margin = band_margin(ends, (nx, ny, nz), B, lipschitz)
-        scratch = self.empty(nbytes, dtype=torch.uint8)
         totals = self.empty(2, dtype=torch.int64)
         axp, st = [ptr(a) for a in ax], self.st()
 
@@ -699,23 +717,15 @@ class Engine:
     # ---- connected components, largest-component filter, nearest neighbour (csrc/mesh.hip) ----------------------------
     def _mesh_args(self, tris, n_verts, what):
         """``tris`` as the library reads it (int32 [T, 3], contiguous, on this device) and V, checked: one read-back of the index range."""
-        if tris.dim() != 2 or tris.shape[1] != 3 or tris.device != self.device or tris.dtype not in (torch.int32, torch.int64):
-            raise _lib.EndoSurfHipError(f"{what} takes [T, 3] int32 / int64 triangles on {self.device} (got {tris.dtype} {tuple(tris.shape)} "
-                                        f"on {tris.device})")
-        V, T = int(n_verts), int(tris.shape[0])
+        t32 = self._tri_arg(tris, what)
+        V, T = int(n_verts), int(t32.shape[0])
         if V < 0 or V >= 1 << 31 or T >= 1 << 31:
             raise _lib.EndoSurfHipError(f"{what}: {V} vertices / {T} triangles do not fit int32 indices")
         if T:
             lo, hi = (int(v) for v in torch.stack([tris.min(), tris.max()]).tolist())
             if lo < 0 or hi >= V:
                 raise _lib.EndoSurfHipError(f"{what}: triangle indices {lo}..{hi} outside [0, {V})")
-        return tris.detach().to(torch.int32).contiguous(), V, T
-
-    def _mesh_scratch(self, V, T):
-        nbytes = int(self.lib.es_mesh_scratch_bytes(V, T))
-        if nbytes < 0:
-            check(1, "es_mesh_scratch_bytes")
-        return self.empty(nbytes, dtype=torch.uint8)
+        return t32, V, T
 
     def _mesh_components(self, t32, V, T, scratch):
         st = self.st()
@@ -743,21 +753,19 @@ class Engine:
         (-1 = degenerate), component_triangles [V], stats), int32 device tensors; ``stats``: components (with a triangle),
         max_triangles, kept_triangles (= the non-degenerate ones here), degenerate, rounds.  The host reads one integer per round."""
         t32, V, T = self._mesh_args(tris, n_verts, "mesh_components")
-        return self._mesh_components(t32, V, T, self._mesh_scratch(V, T))
+        return self._mesh_components(t32, V, T, self._scratch("es_mesh_scratch_bytes", V, T))
 
     def keep_components(self, verts: torch.Tensor, tris: torch.Tensor, keep_ratio: float = 0.9, compact: bool = True):
         """The mesh without the triangles of small components (``meshing.keep_components`` is the numpy twin and the specification):
         a triangle stays iff it is not degenerate and its component has at least ``keep_ratio`` x the triangles of the largest one.
         (verts [V', 3], tris [T', 3] int32, vertex_map [V'] int64, stats); order is kept, ``vertex_map`` is the old index of each new
         vertex (``attr.index_select(0, vertex_map)`` moves per-vertex attributes along).  ``compact=False`` drops triangles only."""
-        if verts.dim() != 2 or verts.shape[1] != 3 or verts.device != self.device:
-            raise _lib.EndoSurfHipError(f"keep_components takes [V, 3] vertices on {self.device} (got {tuple(verts.shape)} on {verts.device})")
+        v32 = self._rows3_arg(verts, "keep_components", "[V, 3] vertices")
         ratio = float(keep_ratio)
         if not 0.0 <= ratio <= 1.0:
             raise _lib.EndoSurfHipError(f"keep_components: keep_ratio must be in [0, 1] (got {keep_ratio!r})")
-        v32 = f32(verts)
         t32, V, T = self._mesh_args(tris, v32.shape[0], "keep_components")
-        scratch, st = self._mesh_scratch(V, T), self.st()
+        scratch, st = self._scratch("es_mesh_scratch_bytes", V, T), self.st()
         _, tlabel, counts, stats = self._mesh_components(t32, V, T, scratch)
         totals = self.empty(2, dtype=torch.int64)
         check(self.lib.es_mesh_keep_count(ptr(t32), V, T, ptr(tlabel), ptr(counts), ratio, stats["max_triangles"], int(bool(compact)),
@@ -773,15 +781,9 @@ class Engine:
         """Exact nearest neighbour of each ``query`` row among the rows of ``points`` ([Q, 3], [P, 3] on this device): (dist [Q] fp32,
         index [Q] int32) by the rule of ``meshing.nearest`` (the numpy twin): fp32 squared distance, ties to the smallest index,
         non-finite rows never an answer, inf / -1 where there is none; bit-identical from call to call.  No read-back."""
-        for name, t in (("query", query), ("points", points)):
-            if t.dim() != 2 or t.shape[1] != 3 or t.device != self.device:
-                raise _lib.EndoSurfHipError(f"nearest takes [N, 3] {name} on {self.device} (got {tuple(t.shape)} on {t.device})")
-        q, p = f32(query), f32(points)
+        q, p = self._rows3_arg(query, "nearest", "[N, 3] query"), self._rows3_arg(points, "nearest", "[N, 3] points")
         Q, P = int(q.shape[0]), int(p.shape[0])
-        nbytes = int(self.lib.es_nn_scratch_bytes(P))
-        if nbytes < 0:
-            check(1, "es_nn_scratch_bytes")
-        scratch, st = self.empty(nbytes, dtype=torch.uint8), self.st()
+        scratch, st = self._scratch("es_nn_scratch_bytes", P), self.st()
         dist, index = self.empty(Q), self.empty(Q, dtype=torch.int32)
         check(self.lib.es_nn_build(ptr(p), P, ptr(scratch), st), "es_nn_build")
         check(self.lib.es_nn_query(ptr(q), Q, P, ptr(scratch), ptr(dist), ptr(index), st), "es_nn_query")
@@ -793,10 +795,8 @@ class Engine:
         through the pinhole camera ``intrinsics`` ([3,3] or [4,4]) at the camera-to-world ``pose`` [4,4] of ``data.get_rays``, in fp64:
         (xy [V, 2] int32 in 1/256-pixel fixed point, zc [V] fp32 camera depth, NaN for a non-finite vertex), on the device."""
         from .meshing import camera_params
-        if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.device != self.device:
-            raise _lib.EndoSurfHipError(f"project_vertices takes [V, 3] vertices on {self.device} (got {tuple(vertices.shape)} on {vertices.device})")
+        v32 = self._rows3_arg(vertices, "project_vertices", "[V, 3] vertices")
         cam = (C.c_double * 17)(*camera_params(intrinsics, pose).tolist())
-        v32 = f32(vertices)
         V = int(v32.shape[0])
         xy, zc = self.empty(V, 2, dtype=torch.int32), self.empty(V)
         check(self.lib.es_rast_project(ptr(v32), V, cam, ptr(xy), ptr(zc), self.st()), "es_rast_project")
@@ -816,10 +816,8 @@ class Engine:
         if xy.dim() != 2 or xy.shape[1] != 2 or xy.dtype != torch.int32 or zc.dim() != 1 or zc.shape[0] != xy.shape[0] \
                 or xy.device != self.device or zc.device != self.device:
             raise _lib.EndoSurfHipError(f"rasterize takes xy [V, 2] int32 and zc [V] on {self.device}")
-        if triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.device != self.device or triangles.dtype not in (torch.int32, torch.int64):
-            raise _lib.EndoSurfHipError(f"rasterize takes [T, 3] int32 / int64 triangles on {self.device} (got {triangles.dtype} "
-                                        f"{tuple(triangles.shape)} on {triangles.device})")
-        V, T = int(zc.shape[0]), int(triangles.shape[0])
+        t32 = self._tri_arg(triangles, "rasterize")
+        V, T = int(zc.shape[0]), int(t32.shape[0])
         att, Cn = None, 0
         if attributes is not None:
             if attributes.dim() != 2 or attributes.shape[0] != V or not 1 <= attributes.shape[1] <= RAST_MAX_ATTRS or attributes.device != self.device:
@@ -832,11 +830,8 @@ class Engine:
                        bary=torch.zeros(H, W, 3, device=self.device), attributes=torch.zeros(H, W, Cn, device=self.device))
             out["stats"]["invalid"] = T
             return out
-        xy32, zc32, t32 = xy.contiguous(), f32(zc), triangles.detach().to(torch.int32).contiguous()
-        nbytes = int(self.lib.es_rast_scratch_bytes(V, T, H, W))
-        if nbytes < 0:
-            check(1, "es_rast_scratch_bytes")
-        scratch, totals, st = self.empty(nbytes, dtype=torch.uint8), self.empty(8, dtype=torch.int64), self.st()
+        xy32, zc32 = xy.contiguous(), f32(zc)
+        scratch, totals, st = self._scratch("es_rast_scratch_bytes", V, T, H, W), self.empty(8, dtype=torch.int64), self.st()
         view = (H, W, float(near), RAST_CULL[cull], ptr(scratch))
         check(self.lib.es_rast_count(ptr(t32), V, T, ptr(xy32), ptr(zc32), *view, ptr(totals), st), "es_rast_count")
         n_work = int(totals[0].item())
@@ -897,9 +892,8 @@ class Engine:
             raise _lib.EndoSurfHipError(f"out must be a contiguous fp64 [{numel}] on {self.device}")
         return out
 
-    def _eval_scratch(self, scratch, nbytes, what):
-        if nbytes < 0:
-            check(1, what)
+    def _eval_scratch(self, scratch, fn_name, *dims):
+        nbytes = self._scratch_bytes(fn_name, *dims)
         if scratch is None:
             return self.empty(max(nbytes, 8), dtype=torch.uint8)
         if scratch.device != self.device or not scratch.is_contiguous() or scratch.numel() * scratch.element_size() < nbytes:
@@ -925,7 +919,7 @@ class Engine:
         if getattr(self, "_ssim_window", None) is None:
             self._ssim_window = torch.from_numpy(ssim_window()).to(self.device).contiguous()
         out = self._eval_out(out, n + 1)
-        scratch = self._eval_scratch(scratch, int(self.lib.es_ssim_scratch_bytes(n, H, W)), "es_ssim_scratch_bytes")
+        scratch = self._eval_scratch(scratch, "es_ssim_scratch_bytes", n, H, W)
         smap = self.empty(n, H - SSIM_WINDOW + 1, W - SSIM_WINDOW + 1, Cn, dtype=torch.float64) if full else None
         check(self.lib.es_ssim(ptr(a), ptr(b), ptr(m), ptr(self._ssim_window), n, H, W, Cn, float(data_range), ptr(scratch), ptr(out), ptr(smap),
                                self.st()), "es_ssim")
@@ -947,7 +941,7 @@ class Engine:
         if H < 1 or W < 1 or not 1 <= Cn <= 16:
             raise _lib.EndoSurfHipError(f"masked_sq_sums needs non-empty images of 1..16 channels (got {H} x {W} x {Cn})")
         out = self._eval_out(out, 2 * n + 2)
-        scratch = self._eval_scratch(scratch, int(self.lib.es_sq_sums_scratch_bytes(n, H, W)), "es_sq_sums_scratch_bytes")
+        scratch = self._eval_scratch(scratch, "es_sq_sums_scratch_bytes", n, H, W)
         check(self.lib.es_masked_sq_sums(ptr(a), ptr(b), ptr(m), n, H, W, Cn, ptr(scratch), ptr(out), self.st()), "es_masked_sq_sums")
         if n == 0:
             out.zero_()
