@@ -1,5 +1,5 @@
-// Opt-in split-precision INFERENCE chain on the register-resident GEMM core (x3r_core.h; formulation and arithmetic in query_x3r.hip /
-// query_x3.hip).  The kernels replace the fp32 launches of point_fwd.hip when a no-grad point evaluation is requested with PF_X3 (no
+// Opt-in split-precision INFERENCE chain on the register-resident GEMM core (x3r_core.h: the arithmetic; query_x3.hip: the
+// formulation).  The kernels replace the fp32 launches of point_fwd.hip when a no-grad point evaluation is requested with PF_X3 (no
 // PF_SAVE); they read and write the same workspace buffers (k_sdf_fwd_x3r and k_color_fwd_x3r are described where they are defined):
 //   k_deform_jvp_x3r   DeformNetwork (reference endosurf.py:724-738) value + forward-mode tangent along the ray direction:
 //                      x_c = x + MLP(x, t) and v = J d.  A wave owns 16 points = 32 columns: lanes 0-15 of a lane half hold the value
@@ -657,7 +657,7 @@ static int infer_attrs() {
     }
     return ST_OK;
 }
-// packed_r = the k-step-ordered split weights of pack_x3r (query_x3r.hip)
+// packed_r = the k-step-ordered split weights of pack_x3 (query_x3.hip)
 // save: the workspace was laid out with PF_SAVE and the kernel keeps what the weight-gradient GEMMs need (training)
 int deform_jvp_x3r(const PointSrc& src, const void* packed_r, const float* weff, float* ws, const WsLayout& L, bool save, hipStream_t st) {
     if (int e = infer_attrs()) return e;

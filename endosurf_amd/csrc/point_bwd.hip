@@ -65,13 +65,12 @@ static int launch_bwd(const BwdArgs& a, int n0, int t0, int n1, int t1, hipStrea
     return ST_OK;
 }
 
-// train_x3r.hip / query_x3.hip
+// train_x3r.hip
 int deform_tan_x3r(const PointSrc& src, const void* packed_r, const float* weff, float* ws, const WsLayout& L, const float* d_go, hipStream_t st, int m_rows = 0);
 int deform_bwd_x3r_with_tail(const BwdArgs& ba, const void* packed_r, int m_main, hipStream_t st);
 int color_bwd_x3r(const PointSrc& src, const void* packed_r, const float* weff, float* ws, const WsLayout& L, bool deform, int m_color, const float* d_rgb,
                   hipStream_t st);
 int deform_bwd_x3r(const void* packed_r, const float* weff, float* ws, const WsLayout& L, int M, int m_color, hipStream_t st);
-const void* packed_x3r_part(const void* packed_x3);
 
 int point_backward_chains(const PointSrc& src, const float* packed, const float* weff, float* ws, int flags, int m_color,
                           const float* d_sdf, const float* d_go, const float* d_rgb, hipStream_t st, const void* packed_x3) {
@@ -86,23 +85,22 @@ int point_backward_chains(const PointSrc& src, const float* packed, const float*
         // the workspace comes from the split-precision training chain (point_fwd.hip): its backward on the register-resident core
         // (train_x3r.hip): colour reverse sweep | deformation tangent sweep | SDF backward (fp32 kernel) | deformation reverse sweep
         if (!packed_x3) return fail(ST_BAD_ARG, "point_backward_chains", "PF_X3_CHAIN needs the split weights (es_pack_x3)");
-        const void* pr = packed_x3r_part(packed_x3);
         if (deform && aux_tail(flags, a.M_color, src.M) && a.M_color % 128 == 0) {
             // the forward's tail arrangement (point_fwd.hip) mirrored: the tail on the fp32 family, its tangent + SDF-backward stages at the
             // head of this family's deformation reverse sweep (train_x3r.hip k_deform_bwd_x3r_tail):
             //   colour_bwd(main) | tan(main) | sdf_bwd(main, fp32) | [tan + sdf_bwd](tail, fp32) + deform_bwd(main) | deform_bwd(tail, fp32)
             const int Mc = a.M_color;
-            if (int e = color_bwd_x3r(src, pr, weff, ws, a.L, deform, Mc, d_rgb, st)) return e;
-            if (int e = deform_tan_x3r(src, pr, weff, ws, a.L, d_go, st, Mc)) return e;
+            if (int e = color_bwd_x3r(src, packed_x3, weff, ws, a.L, deform, Mc, d_rgb, st)) return e;
+            if (int e = deform_tan_x3r(src, packed_x3, weff, ws, a.L, d_go, st, Mc)) return e;
             { ScopedTimer tm(KID_SDF_BWD, Mc, st); if (int e = launch_bwd<BB_NONE, BB_SDF>(a, 0, 0, Mc / TM, 0, st)) return e; }
-            if (int e = deform_bwd_x3r_with_tail(a, pr, Mc, st)) return e;
+            if (int e = deform_bwd_x3r_with_tail(a, packed_x3, Mc, st)) return e;
             { ScopedTimer tm(KID_DEFORM_BWD, Mp - Mc, st); if (int e = launch_bwd<BB_NONE, BB_DEFORM_HALF>(a, 0, 0, (Mp - Mc) / 16, Mc / 16, st)) return e; }
             return hip_last("point_backward_chains");
         }
-        if (flags & PF_COLOR) { if (int e = color_bwd_x3r(src, pr, weff, ws, a.L, deform, a.M_color, d_rgb, st)) return e; }
-        if (deform) { if (int e = deform_tan_x3r(src, pr, weff, ws, a.L, d_go, st)) return e; }
+        if (flags & PF_COLOR) { if (int e = color_bwd_x3r(src, packed_x3, weff, ws, a.L, deform, a.M_color, d_rgb, st)) return e; }
+        if (deform) { if (int e = deform_tan_x3r(src, packed_x3, weff, ws, a.L, d_go, st)) return e; }
         { ScopedTimer tm(KID_SDF_BWD, src.M, st); if (int e = launch_bwd<BB_NONE, BB_SDF>(a, 0, 0, Mp / TM, 0, st)) return e; }
-        if (deform) { if (int e = deform_bwd_x3r(pr, weff, ws, a.L, src.M, a.M_color, st)) return e; }
+        if (deform) { if (int e = deform_bwd_x3r(packed_x3, weff, ws, a.L, src.M, a.M_color, st)) return e; }
         return hip_last("point_backward_chains");
     }
     if (deform && aux_tail(flags, a.M_color, src.M)) {

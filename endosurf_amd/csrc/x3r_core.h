@@ -1,12 +1,44 @@
-// Core of the register-resident split-precision kernels (query_x3r.hip, infer_x3r.hip): the k-step-ordered weight stream, the
-// operand fragments and the GEMM of one layer.  See query_x3r.hip for the formulation.
+// Core of the OPT-IN split-precision kernels (query_x3.hip, infer_x3r.hip, train_x3r.hip): the exact 3-way bf16 split, the
+// k-step-ordered weight stream, the operand fragments and the GEMM of one layer.  See query_x3.hip for the register-resident formulation.
+//
+// fp32 MFMA runs at 1/16 of the bf16 matrix rate on gfx950.  Every fp32 operand is therefore split into three bf16 planes
+//      x = x_h + x_m + x_l,   x_h = bf16(x), x_m = bf16(x - x_h), x_l = bf16(x - x_h - x_m)      (round to nearest even)
+// which is exact for a 24-bit significand, and the product of two fp32 numbers is formed from the six partial products whose
+// weight is >= 2^-16 of the leading one:
+//      x w ~= x_h w_h + (x_h w_m + x_m w_h) + (x_h w_l + x_m w_m + x_l w_h)          (dropped terms <= 2^-23 |x w|)
+// on v_mfma_f32_32x32x16_bf16 with fp32 accumulation: 6 bf16 MFMAs replace 8 fp32 MFMAs of the same tile at 1/2 the cycles each,
+// i.e. 2.67x the fp32 matrix rate at fp32-class accuracy (the tests hold this family to the SAME budgets as the fp32 kernels).
 #pragma once
 #include "chain_common.h"
-#include "x3_common.h"
 
 namespace es {
 
-// segments in the order the kernels walk them: [0, 8) deformation forward, [8, 17) SDF forward (query_x3r.hip, infer_x3r.hip value
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {      // round-to-nearest-even pack of two floats
+    unsigned r;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+    return r;
+}
+// (x0, x1) -> three packed bf16 pairs with x = h + m + l exactly (24-bit significand)
+__device__ __forceinline__ void split_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
+    h = cvt_pk_bf16(x0, x1);
+    float r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xffff0000u);
+    m = cvt_pk_bf16(r0, r1);
+    r0 -= __uint_as_float(m << 16); r1 -= __uint_as_float(m & 0xffff0000u);
+    l = cvt_pk_bf16(r0, r1);
+}
+
+// softplus(beta = 100) on the raw v_exp_f32 / v_log_f32 (base 2): max(z, 0) + 0.01 ln 2 log2(1 + 2^(-100 log2(e) |z|)).  The argument of
+// the logarithm is in (1, 2], so none of the range handling of the library forms is needed: 6 VALU instructions instead of ~25,
+// absolute error < 1e-9 (chain_common.h softplus100 is the form the fp32 kernels use).
+__device__ __forceinline__ float softplus100_native(float z) {
+    const float e = __builtin_amdgcn_exp2f(-144.26950408889634f * fabsf(z));
+    return fmaf(0.006931471805599453f, __builtin_amdgcn_logf(1.f + e), fmaxf(z, 0.f));
+}
+
+// segments in the order the kernels walk them: [0, 8) deformation forward, [8, 17) SDF forward (query_x3.hip, infer_x3r.hip value
 // passes), [17, 25) deformation reverse DR7 .. DR0 (the VJP sweep of infer_x3r.hip), [25, 35) the geometry-feature layer and the SDF
 // reverse sweep (the encoding part of the skip layer's adjoint before its hidden part: both read the same operand), [35, 46) colour
 constexpr int XR_SEGS[] = {DF0, DF1, DF2, DF3, DF4, DF5, DF6, DF7, SF0, SF1, SF2, SF3, SF4M, SF4A, SF5, SF6, SF7,

@@ -242,8 +242,9 @@ class Engine:
 
     def _use_x3(self, M: int) -> bool:
         # small batches (the 1024-point secant queries, the 8 192-point up-sampling queries) are latency-bound chains: they stay on the
-        # 16-point fp32 tiles.  The library's split-precision query runs 32-point LDS-resident tiles up to 8 192 points, measured SLOWER
-        # there (0.27 vs 0.21 ms at 8 192 points, 0.27 vs 0.17 at 1 024: DESIGN 4, round 3), so the threshold stays above them
+        # 16-point fp32 tiles.  The library's split-precision query runs 128-point register-resident blocks whatever the batch size: 64
+        # blocks at 8 192 points leave most of the chip idle, and a 32-point split tile built for these sizes measured SLOWER than fp32
+        # (0.27 vs 0.21 ms at 8 192 points, 0.27 vs 0.17 at 1 024: DEAD_ENDS B4), so the threshold stays above them
         return self.split_precision and M >= self.x3_query_min
 
     def query_sdf(self, pts: es_points, weff, packed, use_deform: bool, tile_points: int = 0) -> torch.Tensor:

@@ -1,4 +1,4 @@
-"""The OPT-IN split-precision family (csrc/infer_x3r.hip, query_x3r.hip, x3r_core.h) through the shape tests of the fp32 family
+"""The OPT-IN split-precision family (csrc/infer_x3r.hip, query_x3.hip, x3r_core.h) through the shape tests of the fp32 family
 (test_gpu_forward_shapes.py): row by row against the fp64 oracle, MAXIMUM gates, points screened away from the ReLU kinks, at the
 family's own tile edges (a wave owns 16 points in k_deform_jvp_x3r, 32 in the VJP / SDF / colour kernels, 128-point blocks in
 k_query_sdf_x3r), NaN-filled workspaces.

@@ -1,6 +1,7 @@
-"""GPU parity of the OPT-IN split-precision SDF query (csrc/query_x3.hip: fp32 operands split exactly into three bf16 planes, six
-partial products on the bf16 matrix pipes, fp32 accumulation) -- held to the SAME budgets as the fp32 query kernel
-(tests/test_gpu_query.py): 1e-5 absolute against the fp64 oracle and the reference's fp64 sdf vectors."""
+"""GPU parity of the OPT-IN split-precision SDF query (csrc/query_x3.hip, k_query_sdf_x3r: fp32 operands split exactly into three bf16
+planes, six partial products on the bf16 matrix pipes, fp32 accumulation) -- held to the SAME budgets as the fp32 query kernel
+(tests/test_gpu_query.py): 1e-5 absolute against the fp64 oracle and the reference's fp64 sdf vectors.  The engine sends this kernel
+8 193 points and more; the small sizes here run its partial 128-point blocks through the C ABI."""
 import ctypes as C
 
 import numpy as np
@@ -61,10 +62,10 @@ def test_query_sdf_x3_ray_samples_golden():
     # strided output + ray_done skipping (the block-wise ray-marching form)
     out = torch.zeros(N, 2 * n, device="cuda")
     done = torch.zeros(N, dtype=torch.int32, device="cuda")
-    done[: (N // 2) // 2 * 2] = 1                      # rays of whole 64-point tiles (2 rays x 32 samples) are skipped
+    done[: (N // 2) // 2 * 2] = 1                      # rays of whole 128-point blocks (4 rays x 32 samples) are skipped
     got2 = _query_x3(lib, _lib, weff, True, ld_out=2 * n, ray_done=done, out=out, rays=rays, z=z, mode=1, n_per_ray=n, ldz=n, M=N * n)
     k = int(done.sum())
-    # (the flat small-batch call above runs the 32-point tiles, the strided one the 128-point blocks: same arithmetic, other summation order)
+    # (the flat call above and the strided one run the same 128-point blocks of k_query_sdf_x3r)
     assert torch.all(got2[:k] == 0) and np.max(np.abs(got2[k:, :n].numpy() - got.numpy()[k:])) < 2e-6 and torch.all(got2[:, n:] == 0)
 
 
