@@ -3,6 +3,12 @@
 // All per-point tensors are row-major [Mp][ld] with Mp = M rounded up to a multiple of 128 (two 64-row tiles of the fp32 kernels = one
 // 128-point block of the register-resident split-precision kernels) so that tiles never
 // need row guards; rows >= M carry finite junk in forward buffers and exact zeros in every adjoint buffer.
+// The backward's TANGENT buffers (WS_S_TAU0, WS_S_TAU, WS_D_T0, WS_D_T, WS_JU) count as adjoint buffers here: they are linear, without
+// a bias, in seeds that the chains read as 0 on rows >= M (d_go, and through it J gbar_o; the colour network's adjoint of g_c), so their
+// rows >= M are exact zeros.  The weight-gradient GEMMs (wgrad.hip) rely on it: the partners of these buffers are FORWARD buffers whose
+// pad rows are junk (WS_D_R, WS_S_RHO and, for the last deformation layer, WS_GC), and the column sum of tau_8 has no partner at all.
+// Nothing is promised about: columns at or beyond the valid width of a buffer (any row), the fourth lane of the [..][4] buffers, and
+// the rows [m_color, M) of the colour network's buffers behind a colour-less tail -- no kernel may let them reach a result.
 // The four [8][Mp][256] stacks of the SDF kernels (WS_S_ACT, WS_S_RHO, WS_S_TAU, WS_S_ZB) are NOT row-major: each [64 x 256] tile
 // is stored in accumulator-fragment order (chain_common.h frag_off) because the SDF epilogues load and store them per quad.
 // Deformation-network value/JVP buffers have 2 rows per point: row 2p = value, row 2p+1 = tangent along the ray direction d
