@@ -38,11 +38,18 @@ def _newest_header_mtime():
     return max(os.path.getmtime(h) for h in hs)
 
 
+def stale_objects(objdir: str, srcs) -> list:
+    """Objects and their .flags stamps in ``objdir`` whose .hip source is not among ``srcs`` (a source that was moved or deleted)."""
+    live = {s.replace(".hip", ".o") for s in srcs}
+    return sorted(os.path.join(objdir, f) for f in os.listdir(objdir)
+                  if (f.endswith(".o") and f not in live) or (f.endswith(".o.flags") and f[:-len(".flags")] not in live))
+
+
 def _compile(src: str, force: bool, extra):
     obj = os.path.join(OBJDIR, src.replace(".hip", ".o"))
     srcp = os.path.join(CSRC, src)
-    # an object is reused only if it was built with the SAME code-generation flags (-D...): a dev build (-DES_DEV_SWITCHES) followed by
-    # a plain build must not link dev objects into the product library
+    # an object is reused only if it was built with the SAME code-generation flags: objects of a -save-temps or -D... build must not be
+    # linked into the product library by the plain build that follows
     codegen = " ".join([*FLAGS, *[e for e in extra if not e.startswith("-R")]])
     stamp = obj + ".flags"
     same_flags = os.path.exists(stamp) and open(stamp).read() == codegen
@@ -62,6 +69,8 @@ def build(force: bool = False, verbose: bool = True, extra=()) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     os.makedirs(OBJDIR, exist_ok=True)
     srcs = sources()
+    for f in stale_objects(OBJDIR, srcs):
+        os.remove(f)
     with cf.ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
         res = list(ex.map(lambda s: _compile(s, force, list(extra)), srcs))
     objs = [r[0] for r in res]

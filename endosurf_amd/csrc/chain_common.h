@@ -63,7 +63,7 @@ __device__ __forceinline__ void gemm_seg(f32x16 (&acc)[RTC][NTC], const float* A
     const float4* wl = W + lane;
     // A-operand addresses: element (k, r) with k = 8G + 2j + hi sits at 512G + 128j + 64hi + (r ^ (4hi) ^ (32(G&1) + 8j)).
     // The XOR takes 8 values (c = 4(G&1) + j): 8 per-lane registers per row tile, everything else is an immediate offset,
-    // so the MFMA stream carries no address arithmetic (the run-time swizzle cost ~8 % of the loop; tools/micro/chain_micro).
+    // so the MFMA stream carries no address arithmetic (the run-time swizzle cost ~8 % of the loop; tools/micro/chain_micro.hip).
     int aoff[RTC][8];
 #pragma unroll
     for (int ri = 0; ri < RTC; ++ri)

@@ -21,11 +21,6 @@
 
 namespace es {
 
-#ifdef ES_PROFILE_BWD        // dev builds only: cycle stamps of block 0 / thread 0 inside sdf_bwd_tile (tools/dev/bwd_profile.py)
-__device__ long long b_prof[256];
-extern "C" int es_debug_b_profile(long long* out, int n) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(b_prof), sizeof(long long) * (n < 256 ? n : 256)); }
-#endif
-
 // Two-segment launches as in point_fwd.hip: the tail's two dependent stages ride in the halves of the main deformation launch
 //   colour_bwd(main) | sdf_bwd(main) | sdf_bwd(tail) + deform_bwd(main, 1st half) | deform_bwd(tail) + deform_bwd(main, 2nd half)
 enum BwdBody { BB_NONE = 0, BB_COLOR, BB_SDF, BB_DEFORM, BB_TAN, BB_TAN_SDF, BB_DEFORM_HALF };

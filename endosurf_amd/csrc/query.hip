@@ -13,20 +13,6 @@
 
 namespace es {
 
-#ifdef ES_PROFILE_QUERY      // dev builds only: cycle stamps of block 0 / thread 0 at the phase boundaries (tools/dev/q_profile.py)
-__device__ long long q_prof[192];      // [0, 64): block 0 (first round) | [64, 128): the last block (last round) | [128, 192): their wall clocks (100 MHz)
-#define Q_STAMP(i) do { if (threadIdx.x == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1)) { \
-        const int b_ = blockIdx.x == 0 ? 0 : 64; q_prof[b_ + (i)] = __builtin_readcyclecounter(); \
-        if ((i) == 0 || (i) == 7) q_prof[128 + (b_ >> 1) + (i)] = wall_clock64(); } } while (0)
-extern "C" int es_debug_q_profile(long long* out, int n) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(q_prof), sizeof(long long) * (n < 192 ? n : 192)); }
-__device__ long long q_times[2 * 4096];      // wall clock (100 MHz) at the start and the end of every block of the last launch (<= 4096 blocks)
-#define Q_BLOCK_TIME(e) do { if (threadIdx.x == 0 && blockIdx.x < 4096) q_times[2 * blockIdx.x + (e)] = wall_clock64(); } while (0)
-extern "C" int es_debug_q_times(long long* out, int n) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(q_times), sizeof(long long) * (n < 8192 ? n : 8192)); }
-#else
-#define Q_STAMP(i) do {} while (0)
-#define Q_BLOCK_TIME(e) do {} while (0)
-#endif
-
 // HALF: latency-bound small batches (secant iterations, 8-sample up-sampling queries) use 32-point tiles: the LDS tile keeps
 // its 64-row layout but only row-tile 0 carries points, so every layer issues half the MFMAs and twice as many workgroups
 // share the batch.
@@ -55,8 +41,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_query_sdf(PointSrc src, Tabs tb
 
     const QuadOff<RTC> qo = quad_offsets<RTC>(0, 2 * wave, lane);
     auto bias2 = [&](float(&b)[2], const float* __restrict__ bias) { b[0] = bias[64 * wave + (lane & 31)]; b[1] = bias[64 * wave + 32 + (lane & 31)]; };
-    Q_STAMP(0);
-    Q_BLOCK_TIME(0);
     if (tid < 64) {
         float x[3], t, d[3];
         load_point(src, tid < PTS ? row0 + tid : src.M, x, t, d);
@@ -70,7 +54,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_query_sdf(PointSrc src, Tabs tb
         encode1<6>(aux, 39, pt, tid);
         zero_rows(aux, 52, 56, tid);
         __syncthreads();
-        Q_STAMP(1);
         float bc[2], bn[2];   // this layer's and the NEXT layer's bias of this lane's two columns (requested a layer ahead)
         bias2(bn, weff + tb.boff[NET_D * LAYERS + 0]);
         {
@@ -87,16 +70,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_query_sdf(PointSrc src, Tabs tb
             });
         }
         __syncthreads();
-        Q_STAMP(2);
 #pragma unroll 1
         for (int l = 1; l <= 7; ++l) {
             f32x16 acc[RTC][2];
             acc_zero(acc);
             bc[0] = bn[0]; bc[1] = bn[1];
             if (l < 7) bias2(bn, weff + tb.boff[NET_D * LAYERS + l + 1]);
-            Q_STAMP(10 + l);
             gemm_seg<32, RTC, 2>(acc, mainT, packed + tb.segoff[DF0 + l], 0, 2 * wave, lane);
-            Q_STAMP(20 + l);
             __syncthreads();
             if (l == 3 && wave == 3) {      // (wave-uniform: the skip's address arithmetic stays out of every other epilogue)
                 for_quads_off(acc, qo, 0, 2 * wave, lane, [&](int row, int col, float(&v)[4], int off, int ni) {
@@ -119,7 +99,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_query_sdf(PointSrc src, Tabs tb
             }
             __syncthreads();
         }
-        Q_STAMP(3);
         smalln_partial<3>(mainT, weff + tb.woff[NET_D * LAYERS + 8], 256, red, tid);
         __syncthreads();
         if (tid < 192) {
@@ -130,7 +109,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_query_sdf(PointSrc src, Tabs tb
     }
 
     // ---- SDF MLP on x_c, output column 0 only ----
-    Q_STAMP(4);
     encode3<6>(aux, 0, px, tid);
     zero_rows(aux, 39, 40, tid);
     __syncthreads();
@@ -150,14 +128,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_query_sdf(PointSrc src, Tabs tb
         });
     }
     __syncthreads();
-    Q_STAMP(5);
 #pragma unroll 1
     for (int l = 1; l <= 7; ++l) {
         f32x16 acc[RTC][2];
         acc_zero(acc);
         bc[0] = bn[0]; bc[1] = bn[1];
         if (l < 7) bias2(bn, weff + tb.boff[NET_S * LAYERS + l + 1]);
-        Q_STAMP(30 + l);
         const int seg = l <= 4 ? SF0 + l : SF0 + l + 1;
         gemm_seg<32, RTC, 2>(acc, mainT, packed + tb.segoff[seg], 0, 2 * wave, lane);
         if (l == 4) gemm_seg<5, RTC, 2>(acc, aux, packed + tb.segoff[SF4A], 0, 2 * wave, lane);   // NeRF skip: + enc part
@@ -170,11 +146,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_query_sdf(PointSrc src, Tabs tb
         });
         __syncthreads();
     }
-    Q_STAMP(6);
     smalln_partial<1>(mainT, weff + tb.woff[NET_S * LAYERS + 8], 256, red, tid);
     __syncthreads();
-    Q_STAMP(7);
-    Q_BLOCK_TIME(1);
     if (tid < PTS && row0 + tid < src.M) {
         const int i = row0 + tid;
         const size_t o = ld_out > 0 ? (size_t)(i / src.n_per_ray) * ld_out + (i % src.n_per_ray) : (size_t)i;   // [ray][ld_out] or flat

@@ -58,11 +58,7 @@ __device__ __forceinline__ void wstream16_next_window(WStream16& ws) {
 // k-group g of the stream's segment into ring slot g & 3 (g is a compile-time constant at every call site)
 __device__ __forceinline__ void ring16_load(Ring16& R, const WStream16& ws, int g) {
     const int slot = g & 3;
-#ifdef ES_Q16_NO_W          // dev probe: every k-group of every layer reads the same (L1-resident) weights
-    const int gl = -4;
-#else
     const int gl = (g & 7) - 4;
-#endif
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) R.b[slot][ni] = ws.p[ni][gl * 64];
 }

@@ -30,9 +30,6 @@
 
 namespace es {
 
-#ifdef XR_PROFILE
-__device__ long long xr_prof[512];
-#endif
 constexpr int XR_PTS = 128;
 constexpr int XR_LDS_BYTES = XR_RING * XR_CHUNK_BYTES + (XR_PTS * XR_ENC_LD + 16 * 256 + 4 * 256 + 4) * 4;
 static_assert(XR_LDS_BYTES <= 160 * 1024, "LDS carve");
@@ -91,7 +88,6 @@ __global__ __launch_bounds__(XR_THREADS, 1) void k_query_sdf_x3r(PointSrc src, T
         for (int r = r_first; r <= r_last; ++r) all_done = all_done && ray_done[r] != 0;
         if (all_done) return;       // workgroup-uniform
     }
-    XR_STAMP(0);
     const int prow = wave * 32 + n;              // this lane's point inside the tile (both lane halves hold the same point)
     float* erow = encs + prow * XR_ENC_LD;
     float x[3], t, dd[3];
@@ -186,13 +182,11 @@ __global__ __launch_bounds__(XR_THREADS, 1) void k_query_sdf_x3r(PointSrc src, T
         __syncthreads();
         ws.start();
     }
-    XR_STAMP(1);
     init8(C, biasL + 8 * 256, hi);
     gemm_r<4>(C, ws, enc_val);
     copy8(P, C);
 #pragma unroll 1
     for (int l = 1; l <= 7; ++l) {
-        XR_STAMP(10 + l);
         init8(C, biasL + (8 + l) * 256, hi);
         gemm_r<16>(C, ws, [&](int s, int j) -> float {
             const int b = s >> 1, q = 2 * (s & 1) + (j >> 2), i = j & 3;
@@ -201,7 +195,6 @@ __global__ __launch_bounds__(XR_THREADS, 1) void k_query_sdf_x3r(PointSrc src, T
         if (l == 4) gemm_r<4>(C, ws, enc_val);             // NeRF skip: + encoding part (chunks of SF4A follow those of SF4M)
         copy8(P, C);
     }
-    XR_STAMP(18);
     {
         float s0 = 0.f;
 #pragma unroll
@@ -218,18 +211,7 @@ __global__ __launch_bounds__(XR_THREADS, 1) void k_query_sdf_x3r(PointSrc src, T
             sdf_out[o] = s0 + b8[3];
         }
     }
-    XR_STAMP(19);
 }
-
-#ifdef XR_PROFILE
-extern "C" int es_debug_xr_profile(long long* out, int n) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(xr_prof), sizeof(long long) * (n < 512 ? n : 512));
-}
-extern "C" int es_debug_xr_reset() {
-    static long long z[512];
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(xr_prof), z, sizeof(z));
-}
-#endif
 
 size_t packed_x3_bytes() { return (size_t)(XR_CHUNKS + XR_PAD_CHUNKS) * XR_CHUNK_BYTES; }
 

@@ -22,14 +22,6 @@
 
 namespace es {
 
-#ifdef ES_PROFILE_WGRAD       // dev builds only: cycle stamps of block 0 / thread 0 inside the fp32 task (tools/dev/wgrad_profile.py)
-__device__ long long w_prof[128];
-#define W_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) w_prof[i] = __builtin_readcyclecounter(); } while (0)
-extern "C" int es_debug_w_profile(long long* out, int n) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(w_prof), sizeof(long long) * (n < 128 ? n : 128)); }
-#else
-#define W_STAMP(i) do {} while (0)
-#endif
-
 constexpr int WG_MAX_PROBS = 20;
 
 struct WgProb {
@@ -62,14 +54,9 @@ constexpr size_t WG_DET_FLOATS = WG_DET_SMALL_OFF + (size_t)WG_MAX_SMALL * WG_MA
 
 // task index of a problem <-> (k block, row chunk).  The kblk tasks of one row chunk read the same dA rows: they get block ids 8
 // apart (same XCD under the round-robin block -> XCD dispatch, started back to back) so that the second reader hits that XCD's
-// L2 instead of HBM
-#ifdef ES_WG_NOPAIR      // dev builds only (A/B of DEAD_ENDS C5): the k-block tasks of a row chunk on NEIGHBOURING block ids (different XCDs)
-constexpr bool WG_PAIR = false;
-#else
-constexpr bool WG_PAIR = true;
-#endif
+// L2 instead of HBM (without the pairing they fetch a quarter more and take the same time: DEAD_ENDS C5)
 __host__ __device__ inline void wg_decode(int local, int kblk, int nchunk, int& kb, int& mc) {
-    if (WG_PAIR && kblk == 2) {
+    if (kblk == 2) {
         const int grp = local / 16, j = local % 16;
         const int full = (nchunk / 8) * 8;                 // chunks covered by complete groups of 8
         if (grp * 8 < full) { mc = grp * 8 + (j & 7); kb = j >> 3; }
@@ -77,7 +64,7 @@ __host__ __device__ inline void wg_decode(int local, int kblk, int nchunk, int& 
     } else { kb = local % kblk; mc = local / kblk; }
 }
 __host__ __device__ inline int wg_encode(int kb, int mc, int kblk, int nchunk) {
-    if (WG_PAIR && kblk == 2) {
+    if (kblk == 2) {
         const int full = (nchunk / 8) * 8;
         return mc < full ? (mc / 8) * 16 + (mc & 7) + 8 * kb : 2 * full + (((mc - full) << 1) | kb);
     }
@@ -196,31 +183,18 @@ __device__ __forceinline__ void wgrad_task(const WgProb& P, int kb, int m0, int 
     WG_SSTORE(p0, 0);
     __syncthreads();
 #pragma unroll 1
-    W_STAMP(0);
     for (int st = 0; st < nst; st += 2) {
-        const bool stamp = st == 32;                     // one iteration in the steady state
-        if (stamp) W_STAMP(1);
         // (Issuing these loads unconditionally -- clamped to the last stage -- lets the compiler count outstanding loads exactly
         // (s_waitcnt vmcnt(3) instead of vmcnt(0) before the second stage store); measured: no change, 14.92 vs 14.96 ms per step.)
         if (st + 2 < nst) WG_GLOAD(p0, m0 + WG_R * (st + 2));
         compute(0);
-        if (stamp) W_STAMP(2);
         WG_SSTORE(p1, 1);                                // stage st+1 (loaded one iteration ago)
-        if (stamp) W_STAMP(3);
         __syncthreads();
-        if (stamp) W_STAMP(4);
         if (st + 3 < nst) WG_GLOAD(p1, m0 + WG_R * (st + 3));
         compute(1);
-        if (stamp) W_STAMP(5);
         if (st + 2 < nst) WG_SSTORE(p0, 0);              // stage st+2
-        if (stamp) W_STAMP(6);
         __syncthreads();
-        if (stamp) W_STAMP(7);
     }
-    W_STAMP(8);
-#ifdef ES_PROFILE_WGRAD
-    if (blockIdx.x == 0 && threadIdx.x == 0) w_prof[20] = nst;
-#endif
 #undef WG_GLOAD
 #undef WG_SSTORE
     // acc[t][tp][r]: n = nb*64 + 2*i + t, i = (r&3) + 8*(r>>2) + 4*hi ; k = kb*128 + kh*64 + 2*lo + tp
@@ -260,7 +234,6 @@ __device__ __forceinline__ void wgrad_task(const WgProb& P, int kb, int m0, int 
             else if (tid_e < P.N) atomicAdd(P.bias_out + tid_e, s);
         }
     }
-    W_STAMP(9);
 }
 
 // Slice `slot` of `nslots` of a small problem: thread = (input feature k, row-block parity); 16-row blocks, the loads of two
@@ -412,8 +385,8 @@ __global__ __launch_bounds__(WG_THREADS, 4) void k_wgrad(WgArgs a) {
 //     pinned with sched_barrier; the stage body is branch-free (rows past the chunk's end are staged as zeros through selects).
 // Problems with few input features (first layers, skip columns: K = 39 / 52 / 93) take the same path (their missing columns are
 // whatever the clamped loads return; those output columns are never stored).
-// Measured (tools/dev/wgrad_x3_probe.py: one [1.65 M x 256] x [1.65 M x 256] problem = the deformation launch's rows; tools/dev/pmc_probe.sh;
-// -DES_WX_NO_MFMA / -DES_WX_NO_SPLIT builds): gaussian operands 1.31 ms at 1.56 GHz (MFMA busy 0.61); MFMAs + fragment reads alone
+// Measured (one [1.65 M x 256] x [1.65 M x 256] problem = the deformation launch's rows, whole and with the MFMAs or the split compiled
+// out; the probe and its switches are gone, DEAD_ENDS.md preamble and C1): gaussian operands 1.31 ms at 1.56 GHz (MFMA busy 0.61); MFMAs + fragment reads alone
 // 0.78 ms at 1.80 GHz (busy 0.895); loads + split + panel writes alone 0.60 ms at 1.99 GHz (5.7 TB/s); all-zero operands 0.92 / 0.62 /
 // 0.53 ms -- the clock follows the power drawn, and the parts ADD: a stage costs 3 465 cycles of MFMA stream + ~1 585 for its 257 VALU and
 // 44 memory instructions, interleaved or not.  Two waves per SIMD (8 waves of [64 x 128], stage phases of SIMD partners in lock step or
@@ -547,18 +520,15 @@ __device__ __forceinline__ void wgrad_task_x3(const WgProb& P, int m0, int m1, u
         wx_static_for(std::make_integer_sequence<int, 96>(), [&](auto ic) {
             constexpr int i = decltype(ic)::value;
             constexpr int half = i / 48, q = (i % 48) / 8, t = (i % 8) / 2, j = i % 2;
-#ifndef ES_WX_NO_MFMA
             if constexpr (half == 0)
                 acc[t][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wx_bf16x8, A[t][TA0[q]]), __builtin_bit_cast(wx_bf16x8, B0[j][TB0[q]]),
                                                                     acc[t][j], 0, 0, 0);
             else
                 acc[t][2 + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wx_bf16x8, A[t][TA1[q]]), __builtin_bit_cast(wx_bf16x8, B1[j][TB1[q]]),
                                                                         acc[t][2 + j], 0, 0, 0);
-#endif
             // ---- side work of the slot ----
             if constexpr (i == 7) bias_add(sa, live);
             if constexpr (i >= 2 && i < 8) rdB1(CUR, (i - 2) & 1, 2 - (i - 2) / 2);              // X tiles 2, 3 of this stage: planes 2, 1, 0
-#ifndef ES_WX_NO_SPLIT
             if constexpr (i >= 8 && i < 56 && (i - 8) % 3 == 0) {                                 // 16 pair splits: operand, row group, word
                 constexpr int k = (i - 8) / 3, g = (k / 4) % 2, jj = k % 4;
                 if constexpr (k < 8) split2(sa[8 * g + 2 * jj], sa[8 * g + 2 * jj + 1], live, h, m, l, jj);
@@ -566,15 +536,10 @@ __device__ __forceinline__ void wgrad_task_x3(const WgProb& P, int m0, int m1, u
             }
             if constexpr (i == 18) wr3(WRT, 0, 0, h, m, l);
             if constexpr (i == 30) wr3(WRT, 0, 1, h, m, l);
-#ifndef ES_WX_NO_LOAD
             if constexpr (i >= 32 && i < 48) loadA(sa, reload, i - 32);
-#endif
             if constexpr (i == 42) wr3(WRT, 1, 0, h, m, l);
             if constexpr (i == 54) wr3(WRT, 1, 1, h, m, l);
-#endif
-#ifndef ES_WX_NO_LOAD
             if constexpr (i >= 56 && i < 72) loadB(sb, reload, i - 56);
-#endif
             if constexpr (i >= 60 && i < 66) rdB0(NXT, (i - 60) & 1, (i - 60) / 2);               // next stage, X tiles 0, 1
             if constexpr (i >= 72 && i < 76) rdA(NXT, i - 72, 2);                                 // dA plane 2 died with slot 71
             if constexpr (i >= 88 && i < 92) rdA(NXT, i - 88, 1);                                 // dA plane 1 died with slot 87

@@ -96,11 +96,9 @@ struct WStream {
     FragA a0;                // fragments of (k, group 0), read ahead
     __device__ __forceinline__ int packed_step(int kk) const { return kk < e0 ? b0 + kk : (kk < e1 ? b1 + (kk - e0) : b2 + (kk - e1)); }
     __device__ __forceinline__ void piece(int kk, int i) {
-#ifndef XR_NO_DMA
         const u32x4* src = g + ((size_t)packed_step(kk) * XR_CHUNK_UNITS + wave * 6 + i) * 64 + lane;
         unsigned char* dst = ring + (kk & (XR_RING - 1)) * XR_CHUNK_BYTES + (wave * 6 + i) * 1024;
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-#endif
     }
     // nst: vector-memory STORES the kernel issued after the last load of the pair that is landing (the sink of the even k-step: it runs
     // after that k-step's staging slots, and the odd k-step issues nothing before its barrier).  vmcnt counts loads and stores of gfx9 in
@@ -111,9 +109,7 @@ struct WStream {
         if (nst == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
         else if (nst == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#ifndef XR_NO_BARRIER
         __builtin_amdgcn_s_barrier();
-#endif
     }
     __device__ __forceinline__ void read_group(FragA& a, int kk, int grp) const {
         const u32x4* A = reinterpret_cast<const u32x4*>(ring + (kk & (XR_RING - 1)) * XR_CHUNK_BYTES) + lane;
@@ -129,15 +125,6 @@ struct WStream {
         read_group(a0, k, 0);
     }
 };
-
-#ifdef XR_PROFILE        // dev builds only (tools/dev/xr_profile.sh): cycle stamps of block 0 / wave 0
-extern __device__ long long xr_prof[512];
-#define XR_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) xr_prof[i] = __builtin_readcyclecounter(); } while (0)
-#define XR_ADD(i, v) do { if (blockIdx.x == 0 && threadIdx.x == 0) xr_prof[i] += (v); } while (0)
-#else
-#define XR_STAMP(i) do {} while (0)
-#define XR_ADD(i, v) do {} while (0)
-#endif
 
 struct FragB { u32x4 h, m, l; };
 // SINK: sink(s, v) receives the 8 fp32 operand elements of k-step s (element j <-> k offset xr_kperm(hi, j)) once, right after they
@@ -173,18 +160,15 @@ __device__ __forceinline__ void mfma_group(f32x16 (&C)[8], WStream& ws, const Fr
 #pragma unroll
     for (int t = 0; t < 6; ++t) {
         const u32x4 bt = TB[t] == 0 ? b.h : (TB[t] == 1 ? b.m : b.l);
-#ifndef XR_NO_MFMA
         if (MFMA)
 #pragma unroll
             for (int f = 0; f < NF; ++f)
                 C[4 * G + f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a.p[f][TA[t]]), __builtin_bit_cast(bf16x8, bt),
                                                                       C[4 * G + f], 0, 0, 0);
-#endif
         if (STAGE) {
             ws.piece(ws.k + 2 + G, t);                     // one direct load per four MFMAs
             side(ws.k + 2 + G, t, snext + 1 + G);          // a kernel's own per-k-step operand stream (same slots, same barriers)
         }
-#ifndef XR_NO_VALU
         if (more && t < 4) {
             constexpr int NK = LATE ? (G == 1 ? 2 : 0) : 1;
             const int k0 = LATE ? 2 * t : 4 * G + t;
@@ -199,13 +183,10 @@ __device__ __forceinline__ void mfma_group(f32x16 (&C)[8], WStream& ws, const Fr
                 }
             }
         }
-#endif
-#ifndef XR_NO_PIN
         // keep each term's fillers next to its four MFMAs: left alone, the scheduler gathers the MFMAs into long runs and the VALU work
         // into blocks of ~40 instructions between two of them (measured: 36.3 k -> 33.7 k cycles per 256-wide layer; one barrier per MFMA
         // with the fillers dealt out by hand: 36.5 k)
         __builtin_amdgcn_sched_barrier(0);
-#endif
     }
 }
 template <int NG, bool LATE, bool ODD, class VAL, class SIDE, class SINK>
@@ -289,15 +270,11 @@ __device__ __forceinline__ float dphi_from_s(float s) {
 }
 
 // four consecutive features of one row of a row-major [rows][256] stack.  A row's 128-B line is completed by four such stores (two lane
-// halves x two pieces x two k-steps): ES_X3R_NT_STORES=1 (dev builds) marks them non-temporal like the fp32 kernels' stream-outs; the
-// default leaves them to the L2's write combining (measured: the non-temporal form wrote 1.5-1.66x the bytes at ~2.3 TB/s)
+// halves x two pieces x two k-steps), left to the L2's write combining: marked non-temporal like the fp32 kernels' stream-outs they
+// wrote 1.5-1.66x the bytes at ~2.3 TB/s (DEAD_ENDS D5)
 __device__ __forceinline__ void st4(float* p, float a, float b, float c, float d) {
     const v4f_frag t = {a, b, c, d};
-#ifdef ES_X3R_NT_STORES
-    __builtin_nontemporal_store(t, reinterpret_cast<v4f_frag*>(p));
-#else
     *reinterpret_cast<v4f_frag*>(p) = t;
-#endif
 }
 // the operand of k-step s (8 values: features 16 s + 4 hi .. + 3 and 16 s + 8 + 4 hi .. + 3) into a row whose base already holds + 4 hi
 __device__ __forceinline__ void st_kstep(float* row_hi, int s, const float (&v)[8]) {

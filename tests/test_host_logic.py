@@ -45,6 +45,85 @@ def test_product_never_imports_oracle():
                 assert not re.search(r"^\s*(from|import)\s+oracle", src, flags=re.M), f
 
 
+def _library_sources():
+    import glob
+    import os
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(repo, "endosurf_amd", "csrc")
+    srcs = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert len(srcs) > 30, srcs
+    return srcs, sorted(glob.glob(os.path.join(repo, "include", "*.h")))
+
+
+def test_library_sources_have_one_configuration():
+    """The library is built one way: the only preprocessor conditionals in csrc/ and include/ are include guards, __cplusplus and
+    __HIP_DEVICE_COMPILE__ (no switch that compiles a barrier, a load or an MFMA out of a kernel, no profiling variant)."""
+    import os
+    import re
+    srcs, headers = _library_sources()
+    seen = 0
+    for path in srcs + headers:
+        src = open(path).read()
+        base = os.path.basename(path)
+        guard = re.sub(r"\W", "_", base).upper()          # endosurf_hip.h -> ENDOSURF_HIP_H, and only when the file defines it next
+        for m in re.finditer(r"^[ \t]*#[ \t]*(if|ifdef|ifndef|elif)\b([^\n]*)", src, flags=re.M):
+            seen += 1
+            cond = re.sub(r"//.*|/\*.*?\*/", "", m.group(2))
+            names = set(re.findall(r"[A-Za-z_]\w*", cond)) - {"defined"}
+            allowed = {"__cplusplus", "__HIP_DEVICE_COMPILE__"}
+            if m.group(1) == "ifndef" and re.match(r"\s*#[ \t]*define[ \t]+" + guard + r"\b", src[m.end():]):
+                allowed.add(guard)
+            assert names and names <= allowed, f"{base}: #{m.group(1)}{m.group(2)}"
+    assert seen >= 4          # the header's guard and its two __cplusplus blocks, query16.hip's device-pass typedef
+
+
+def _extern_c_functions(src):
+    """Names with C linkage that a source defines: `extern "C"` one-liners, the non-static functions of `extern "C" { }` blocks, and
+    unindented definitions named es_* (C linkage through the header's declaration)."""
+    import re
+    src = re.sub(r"//[^\n]*|/\*.*?\*/", "", src, flags=re.S)
+    names = set(re.findall(r"^[A-Za-z_][^;{}()=\n]*?\b(es_[a-z0-9_]+)\s*\(", src, flags=re.M))
+    for m in re.finditer(r'extern\s+"C"\s*(\{)?', src):
+        if not m.group(1):
+            names.update(re.findall(r"\A[^;{(]*?\b([A-Za-z_]\w*)\s*\(", src[m.end():]))
+            continue
+        depth, top = 1, []
+        for ch in src[m.end():]:
+            depth += (ch == "{") - (ch == "}")
+            if depth == 0:
+                break
+            if depth == 1:
+                top.append(";" if ch == "}" else ch)
+        for stmt in "".join(top).split(";"):
+            stmt = stmt.strip()
+            if "(" in stmt and not stmt.startswith("static"):
+                names.update(re.findall(r"\b([A-Za-z_]\w*)\s*\(", stmt)[:1])
+    return names
+
+
+def test_every_c_function_of_the_library_is_in_the_abi():
+    """The inverse of tests/test_abi.py: nothing with C linkage is defined in csrc/ that include/endosurf_hip.h and _lib.PROTOTYPES do not
+    declare (a debugging entry point would be one)."""
+    from endosurf_amd import _lib
+    assert _extern_c_functions('namespace es {\nextern "C" int es_probe_x(long long* out, int n) { return 0; }\n}') == {"es_probe_x"}
+    assert _extern_c_functions('extern "C" {\nstatic int helper(int a) { return a; }\nint probe(int a) {\n    return helper(a);\n}\n}') == {"probe"}
+    found = set()
+    for path in _library_sources()[0]:
+        found |= _extern_c_functions(open(path).read())
+    assert found - set(_lib.PROTOTYPES) == set()
+    assert found == set(_lib.PROTOTYPES)          # the parser sees every definition
+
+
+def test_build_selects_objects_without_a_source(tmp_path):
+    from endosurf_amd.build import stale_objects
+    for f in ("a.o", "a.o.flags", "gone.o", "gone.o.flags", "notes.txt"):
+        (tmp_path / f).write_bytes(b"")
+    d = str(tmp_path)
+    assert stale_objects(d, ["a.hip"]) == [str(tmp_path / "gone.o"), str(tmp_path / "gone.o.flags")]
+    assert stale_objects(d, ["a.hip", "gone.hip"]) == []
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["a.o", "a.o.flags", "gone.o", "gone.o.flags", "notes.txt"]      # selects, does not delete
+
+
 def test_unsupported_architecture_is_rejected():
     from endosurf_amd.renderer import _check_arch
     cfg = net_cfg(True)
