@@ -146,12 +146,24 @@ PROTOTYPES = {
     "es_eval_panel_rgb": (_I, [_P, _I, _I, _I, _I, _P, C.c_longlong, _I, _P]),
     "es_eval_panel_depth": (_I, [_P, _I, _I, _I, C.c_double, _P, C.c_longlong, _I, _P]),
     "es_eval_panel_normal": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, C.c_longlong, _I, _P]),
+    "es_mesh_clean_keys": (_I, [_P, C.c_longlong, C.c_longlong, _P, _P, _P]),
+    "es_mesh_clean_count": (_I, [_P, C.c_longlong, C.c_longlong, _P, _I, _P, _P, _P]),
+    "es_vn_scratch_bytes": (C.c_int64, [C.c_longlong]),
+    "es_vn_count": (_I, [_P, C.c_longlong, C.c_longlong, _P, _P, _P]),
+    "es_vn_gather": (_I, [_P, _P, C.c_longlong, C.c_longlong, _P, _P, _P, _P]),
+    "es_cluster_scratch_bytes": (C.c_int64, [C.c_longlong]),
+    "es_cluster_keys": (_I, [_P, C.c_longlong, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P]),
+    "es_cluster_count": (_I, [_P, C.c_longlong, _P, _P, _P]),
+    "es_cluster_emit": (_I, [_P, _P, _I, C.c_longlong, _P, _P, C.c_longlong, C.c_longlong, _P, _P, _P, _P]),
+    "es_cluster_remap": (_I, [_P, C.c_longlong, C.c_longlong, _P, _P, _P]),
+    "es_ply_body_bytes": (C.c_int64, [C.c_longlong, C.c_longlong, _I, _I]),
+    "es_ply_pack": (_I, [_P, _P, _P, _P, C.c_longlong, C.c_longlong, _P, _P]),
     "es_timing_enable": (_I, [_I]),
     "es_timing_drain": (_I, [_I, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "es_kernel_name": (C.c_char_p, [_I]),
 }
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 QUERY_TILE_RACING = 32      # include/endosurf_hip.h ES_QUERY_TILE_RACING
 PF_DEFORM, PF_COLOR, PF_SAVE, PF_X3 = 1, 2, 4, 8
 WS_XC, WS_V, WS_SDF, WS_FEAT, WS_GC, WS_GO, WS_RGB = range(7)

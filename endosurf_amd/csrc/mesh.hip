@@ -11,6 +11,13 @@
 //   k_mesh_stats         components with a triangle, the largest triangle count
 //   k_mesh_keep_flags    triangle kept / vertex used bytes (the fp64 comparison of the reference's numpy line)
 //   scan.h's three (MeshKeepSrc) / k_mesh_keep_emit   stable compaction: the exclusive scan of the two flag arrays, then the copy
+// Clean-up for export (ABI v14; twin: meshing.mesh_clean; contract: DESIGN.md 7e): a triangle with a repeated index goes, and of the
+// triangles with the same three vertex indices (any rotation, either orientation) the one with the smallest triangle index stays:
+//   k_mesh_clean_keys    the sorted corners (a < b < c) of a triangle as two keys: a (32 bits) and b 2^31 + c (62 bits) -- 93 bits in
+//                        all, so no vertex index below 2^31 is folded; a degenerate triangle gets the largest keys
+//   (the caller orders the triangles by (a, b, c, triangle index): two stable sorts)
+//   k_mesh_clean_flags   in that order a triangle whose predecessor has the same corners is a duplicate; tflag / vflag bytes as above
+//   scan.h's three (MeshKeepSrc) / k_mesh_keep_emit   the same compaction as the component filter's
 // Nearest neighbour (exact; fp32 squared distance (dx dx + dy dy) + dz dz without contraction, ties to the smallest index):
 //   k_nn_bbox / k_nn_header     box of the finite points -> the grid (at most one cell per four finite points, at least one per axis)
 //   k_nn_count / scan.h's three (NnSrc) / k_nn_fill   counting sort of the points by cell (z fastest) into (x, y, z, index) records
@@ -244,6 +251,67 @@ __global__ __launch_bounds__(256) void k_mesh_keep_emit(const float* __restrict_
                 }
             }
         }
+    }
+}
+
+// a < b < c of three different indices
+__device__ __forceinline__ void sort3(int& a, int& b, int& c) {
+    int t;
+    if (a > b) { t = a; a = b; b = t; }
+    if (b > c) { t = b; b = c; c = t; }
+    if (a > b) { t = a; a = b; b = t; }
+}
+
+__global__ __launch_bounds__(256) void k_mesh_clean_keys(const int* __restrict__ tris, int V, long long T, int* __restrict__ key_hi,
+                                                         long long* __restrict__ key_lo) {
+    for (long long t = blockIdx.x * 256ll + threadIdx.x; t < T; t += gridDim.x * 256ll) {
+        int a, b, c;
+        if (tri_load(tris, t, V, a, b, c)) {
+            sort3(a, b, c);
+            key_hi[t] = a;
+            key_lo[t] = ((long long)b << 31) | (long long)c;
+        } else {
+            key_hi[t] = 0x7fffffff;
+            key_lo[t] = 0x7fffffffffffffffll;
+        }
+    }
+}
+
+// order[i] = the triangle at place i of the order by (corners, triangle index).  tflag is zeroed before the launch, so an ``order``
+// that is no permutation drops triangles and cannot make a write go astray.
+__global__ __launch_bounds__(256) void k_mesh_clean_flags(const int* __restrict__ tris, int V, long long T, const long long* __restrict__ order,
+                                                          int compact, unsigned char* __restrict__ tflag, unsigned char* vflag,
+                                                          unsigned long long* totals) {
+    __shared__ int part[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int n_deg = 0;
+    for (long long base = blockIdx.x * 256ll; base < T; base += gridDim.x * 256ll) {          // (wave-uniform trip count)
+        const long long i = base + threadIdx.x;
+        if (i >= T) continue;
+        const long long t = order[i];
+        if (t < 0 || t >= T) continue;
+        int a, b, c;
+        if (!tri_load(tris, t, V, a, b, c)) { ++n_deg; continue; }
+        sort3(a, b, c);
+        bool dup = false;
+        if (i > 0) {
+            const long long p = order[i - 1];
+            int pa, pb, pc;
+            if (p >= 0 && p < T && tri_load(tris, p, V, pa, pb, pc)) {
+                sort3(pa, pb, pc);
+                dup = pa == a && pb == b && pc == c;
+            }
+        }
+        if (dup) continue;
+        tflag[t] = 1;
+        if (compact) { vflag[a] = 1; vflag[b] = 1; vflag[c] = 1; }          // (every writer stores the same byte)
+    }
+    n_deg = wscan_add(n_deg, lane);
+    if (lane == 63) part[wv] = n_deg;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int n = part[0] + part[1] + part[2] + part[3];
+        if (n) atomicAdd(totals + 2, (unsigned long long)n);
     }
 }
 
@@ -635,6 +703,32 @@ int es_mesh_keep_emit(const float* verts, const int* tris, long long V, long lon
     hipLaunchKernelGGL(k_mesh_keep_emit, dim3(grid_for(V > T ? V : T)), dim3(256), 0, static_cast<hipStream_t>(stream), verts, tris, (int)V, T, s.voff,
                        s.toff, s.vflag, s.tflag, (int)V2, (int)T2, verts_out, tris_out, vertex_map);
     return hip_last("es_mesh_keep_emit");
+}
+
+int es_mesh_clean_keys(const int* tris, long long V, long long T, int* key_hi, long long* key_lo, void* stream) {
+    if (const int s = mesh_check(V, T)) return s;
+    if (T == 0) return ST_OK;
+    ES_REQUIRE(tris && key_hi && key_lo, "es_mesh_clean_keys needs tris, key_hi and key_lo");
+    hipLaunchKernelGGL(k_mesh_clean_keys, dim3(grid_for(T)), dim3(256), 0, static_cast<hipStream_t>(stream), tris, (int)V, T, key_hi, key_lo);
+    return hip_last("es_mesh_clean_keys");
+}
+
+int es_mesh_clean_count(const int* tris, long long V, long long T, const long long* order, int compact, void* scratch, long long* totals,
+                        void* stream) {
+    if (const int s = mesh_check(V, T)) return s;
+    ES_REQUIRE(totals && (T == 0 || (tris && order)), "es_mesh_clean_count needs tris, order and totals");
+    ES_SCRATCH_OK(scratch, "mesh scratch");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const MeshScratch s = mesh_layout(scratch, V, T);
+    ES_HIP(hipMemsetAsync(totals, 0, 3 * sizeof(long long), st));
+    if (V > 0) ES_HIP(hipMemsetAsync(s.vflag, compact ? 0 : 1, V, st));
+    if (T > 0) {
+        ES_HIP(hipMemsetAsync(s.tflag, 0, T, st));
+        hipLaunchKernelGGL(k_mesh_clean_flags, dim3(grid_for(T)), dim3(256), 0, st, tris, (int)V, T, order, compact, s.tflag, s.vflag,
+                           reinterpret_cast<unsigned long long*>(totals));
+    }
+    scan_launch(MeshKeepSrc{s.vflag, s.tflag, V, T, s.voff, s.toff}, s.nblk, s.bsum, s.boff, totals, st);
+    return hip_last("es_mesh_clean_count");
 }
 
 int64_t es_nn_scratch_bytes(long long n_points) {

@@ -262,3 +262,165 @@ def cal_geometric_error(points, vertices, depth_scale: float = 1.0, engine=None)
     as_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
     dist, _ = nearest(as_np(points), as_np(vertices))
     return float(dist.astype(np.float64).mean()) * float(depth_scale) if dist.size else float("nan")
+
+
+# ---- binary PLY files (the reference's demo writes its meshes through Open3D, trainer_endosurf.py:447-466) ---------------
+PLY_VERTEX_PROPS = ("x", "y", "z")
+PLY_NORMAL_PROPS = ("nx", "ny", "nz")
+PLY_COLOR_PROPS = ("red", "green", "blue")
+PLY_FACE_LINE = "property list uchar int vertex_indices"
+
+
+def ply_header(n_vertices, n_faces=None, colors=False, normals=False, comment=None) -> bytes:
+    """The header ``write_ply`` puts in front of ``ply_body``: ``n_faces=None`` declares no face element (a point cloud)."""
+    lines = ["ply", "format binary_little_endian 1.0"]
+    if comment is not None:
+        for c in str(comment).splitlines() or [""]:
+            lines.append(f"comment {c}")
+    lines.append(f"element vertex {int(n_vertices)}")
+    lines += [f"property float {p}" for p in PLY_VERTEX_PROPS]
+    if normals:
+        lines += [f"property float {p}" for p in PLY_NORMAL_PROPS]
+    if colors:
+        lines += [f"property uchar {p}" for p in PLY_COLOR_PROPS]
+    if n_faces is not None:
+        lines += [f"element face {int(n_faces)}", PLY_FACE_LINE]
+    lines.append("end_header")
+    return ("\n".join(lines) + "\n").encode("ascii")
+
+
+def _ply_vertex_dtype(colors, normals):
+    fields = [(p, "<f4") for p in PLY_VERTEX_PROPS]
+    if normals:
+        fields += [(p, "<f4") for p in PLY_NORMAL_PROPS]
+    if colors:
+        fields += [(p, "u1") for p in PLY_COLOR_PROPS]
+    return np.dtype(fields)          # packed: 12, 24, 15 or 27 bytes
+
+
+_PLY_FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])          # packed: 13 bytes
+
+
+def _ply_rows(a, name, n=None):
+    a = np.asarray(a, np.float32)
+    if a.ndim != 2 or a.shape[1] != 3 or (n is not None and a.shape[0] != n):
+        raise ValueError(f"{name} must be [V, 3]" + (f" with V = {n}" if n is not None else "") + f" (got {a.shape})")
+    return a
+
+
+def ply_body(vertices, triangles=None, colors=None, normals=None) -> np.ndarray:
+    """The body of a ``binary_little_endian 1.0`` PLY file as a uint8 array (numpy twin of ``Engine.ply_pack``).  Per vertex:
+    ``float x y z`` (fp32), then ``float nx ny nz`` when ``normals`` [V, 3] are given, then ``uchar red green blue`` when ``colors``
+    [V, 3] are given.  Colours are floats in [0, 1], quantised by the rule of ``to8b`` on fp32: trunc(255 * clip(c, 0, 1)), the product
+    rounded to fp32 -- so a value below 0 gives 0, a value above 1 gives 255, 1.0 gives 255, 0.5 gives 127, and k / 255 gives k or k - 1
+    as the fp32 product falls; NaN gives 0.  Then per triangle ``uchar 3`` and three ``int`` (int32) indices, 13 bytes.
+    ``triangles=None`` gives a point cloud's body."""
+    v = _ply_rows(vertices, "vertices")
+    rec = np.zeros(len(v), _ply_vertex_dtype(colors is not None, normals is not None))
+    for j, p in enumerate(PLY_VERTEX_PROPS):
+        rec[p] = v[:, j]
+    if normals is not None:
+        nn = _ply_rows(normals, "normals", len(v))
+        for j, p in enumerate(PLY_NORMAL_PROPS):
+            rec[p] = nn[:, j]
+    if colors is not None:
+        c = _ply_rows(colors, "colors", len(v))
+        c8 = to8b(np.where(np.isnan(c), np.float32(0), c))
+        for j, p in enumerate(PLY_COLOR_PROPS):
+            rec[p] = c8[:, j]
+    parts = [np.frombuffer(rec.tobytes(), np.uint8)]
+    if triangles is not None:
+        t = np.asarray(triangles)
+        t = np.zeros((0, 3), np.int32) if t.size == 0 else t
+        if t.ndim != 2 or t.shape[1] != 3 or not np.issubdtype(t.dtype, np.integer):
+            raise ValueError(f"triangles must be an integer [T, 3] array (got {t.dtype} {t.shape})")
+        face = np.zeros(len(t), _PLY_FACE_DTYPE)
+        face["n"] = 3
+        face["v"] = t.astype(np.int32)
+        parts.append(np.frombuffer(face.tobytes(), np.uint8))
+    return np.concatenate(parts)
+
+
+def write_ply(path, vertices, triangles=None, colors=None, normals=None, comment=None, engine=None) -> None:
+    """A mesh or a point cloud as a ``binary_little_endian 1.0`` PLY file: ``ply_header`` then the body of ``ply_body``, whose
+    docstring is the layout and the colour rule.  ``vertices`` [V, 3]; ``triangles`` [T, 3] integers or None (a point cloud: no face
+    element); ``colors`` [V, 3] floats in [0, 1] or None; ``normals`` [V, 3] or None; ``comment``: one header line per line of text.
+    When ``vertices`` is a device tensor the body is packed on the device (``Engine.ply_pack``; the other arrays are moved there if
+    need be; an ``Engine`` of that device is made when none is given) and crosses to the host in one copy; anything else goes through
+    the numpy packer.  Coordinates are written as fp32 (Open3D writes doubles)."""
+    T = None if triangles is None else int(triangles.shape[0]) if hasattr(triangles, "shape") else len(triangles)
+    if torch.is_tensor(vertices) and vertices.is_cuda:
+        engine = _engine_for(vertices, engine)
+        on = lambda a: None if a is None else torch.as_tensor(a).to(engine.device)
+        with torch.cuda.device(engine.device):
+            body = engine.ply_pack(vertices, on(triangles), on(colors), on(normals)).cpu().numpy()
+    else:
+        as_np = lambda a: None if a is None else (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a))
+        body = ply_body(as_np(vertices), as_np(triangles), as_np(colors), as_np(normals))
+    with open(path, "wb") as f:
+        f.write(ply_header(int(vertices.shape[0]) if hasattr(vertices, "shape") else len(vertices), T, colors is not None, normals is not None, comment))
+        f.write(body.tobytes())
+
+
+def read_ply(path) -> Dict[str, np.ndarray]:
+    """What ``write_ply`` wrote, as numpy arrays: ``vertices`` [V, 3] float32, ``triangles`` [T, 3] int32 when the file has a face
+    element, ``normals`` [V, 3] float32 and ``colors`` [V, 3] uint8 when it has them, ``comments`` (a list of strings) when it has any.
+    Raises ValueError for any other PLY file: ascii or big-endian data, other elements, properties, types or orders, faces that are not
+    triangles, a body of the wrong length."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    end = raw.find(b"end_header\n")
+    if not raw.startswith(b"ply\n") or end < 0:
+        raise ValueError(f"{path}: not a PLY file (no 'ply' magic or no end_header line)")
+    try:
+        lines = raw[:end].decode("ascii").split("\n")[1:-1]
+    except UnicodeDecodeError:
+        raise ValueError(f"{path}: the PLY header is not ASCII") from None
+    body = raw[end + len(b"end_header\n"):]
+    if not lines or not lines[0].startswith("format "):
+        raise ValueError(f"{path}: the PLY header has no format line")
+    if lines[0] != "format binary_little_endian 1.0":
+        raise ValueError(f"{path}: only 'format binary_little_endian 1.0' is read (got {lines[0]!r})")
+    comments = [ln[len("comment "):] for ln in lines[1:] if ln.startswith("comment ") or ln == "comment"]
+    rest = [ln for ln in lines[1:] if not (ln.startswith("comment ") or ln == "comment")]
+    if not rest or not rest[0].startswith("element vertex "):
+        raise ValueError(f"{path}: expected 'element vertex N' (got {rest[0] if rest else 'nothing'!r})")
+    try:
+        V = int(rest[0].split()[2])
+    except (IndexError, ValueError):
+        raise ValueError(f"{path}: bad vertex count in {rest[0]!r}") from None
+    face_at = [i for i, ln in enumerate(rest) if ln.startswith("element ") and i > 0]
+    props = rest[1:face_at[0]] if face_at else rest[1:]
+    want = {(c, n): [f"property float {p}" for p in PLY_VERTEX_PROPS] + ([f"property float {p}" for p in PLY_NORMAL_PROPS] if n else [])
+            + ([f"property uchar {p}" for p in PLY_COLOR_PROPS] if c else []) for c in (False, True) for n in (False, True)}
+    match = [k for k, v in want.items() if v == props]
+    if not match:
+        raise ValueError(f"{path}: vertex properties other than float x y z [float nx ny nz] [uchar red green blue]: {props}")
+    has_colors, has_normals = match[0]
+    T = None
+    if face_at:
+        tail = rest[face_at[0]:]
+        if len(tail) != 2 or not tail[0].startswith("element face ") or tail[1] != PLY_FACE_LINE:
+            raise ValueError(f"{path}: after the vertex element only 'element face N' with '{PLY_FACE_LINE}' is read (got {tail})")
+        try:
+            T = int(tail[0].split()[2])
+        except (IndexError, ValueError):
+            raise ValueError(f"{path}: bad face count in {tail[0]!r}") from None
+    vdt = _ply_vertex_dtype(has_colors, has_normals)
+    if V < 0 or (T is not None and T < 0) or len(body) != V * vdt.itemsize + (T or 0) * _PLY_FACE_DTYPE.itemsize:
+        raise ValueError(f"{path}: the body has {len(body)} bytes, the header promises {V} vertices of {vdt.itemsize} bytes"
+                         + (f" and {T} faces of 13" if T is not None else ""))
+    rec = np.frombuffer(body, vdt, count=V)
+    out = {"vertices": np.stack([rec[p] for p in PLY_VERTEX_PROPS], -1).astype(np.float32).reshape(V, 3)}
+    if has_normals:
+        out["normals"] = np.stack([rec[p] for p in PLY_NORMAL_PROPS], -1).astype(np.float32).reshape(V, 3)
+    if has_colors:
+        out["colors"] = np.stack([rec[p] for p in PLY_COLOR_PROPS], -1).astype(np.uint8).reshape(V, 3)
+    if T is not None:
+        face = np.frombuffer(body, _PLY_FACE_DTYPE, count=T, offset=V * vdt.itemsize)
+        if T and (face["n"] != 3).any():
+            raise ValueError(f"{path}: a face that is not a triangle")
+        out["triangles"] = np.ascontiguousarray(face["v"]).astype(np.int32).reshape(T, 3)
+    if comments:
+        out["comments"] = comments
+    return out

@@ -790,6 +790,102 @@ class Engine:
         check(self.lib.es_nn_query(ptr(q), Q, P, ptr(scratch), ptr(dist), ptr(index), st), "es_nn_query")
         return dist, index
 
+    # ---- mesh export: clean-up, normals, clustering, PLY body (csrc/mesh.hip, csrc/export.hip; contract: DESIGN.md 7e) ------
+    def _mesh_clean(self, v32, t32, V, T, compact):
+        """``mesh_clean`` of checked arguments.  The two stable sorts order the triangles by (sorted corners, triangle index)."""
+        st, scratch = self.st(), self._scratch("es_mesh_scratch_bytes", V, T)
+        key_hi, key_lo = self.empty(T, dtype=torch.int32), self.empty(T, dtype=torch.int64)
+        check(self.lib.es_mesh_clean_keys(ptr(t32), V, T, ptr(key_hi), ptr(key_lo), st), "es_mesh_clean_keys")
+        by_lo = torch.sort(key_lo, stable=True).indices
+        order = by_lo[torch.sort(key_hi[by_lo], stable=True).indices].contiguous()
+        totals = self.empty(3, dtype=torch.int64)
+        check(self.lib.es_mesh_clean_count(ptr(t32), V, T, ptr(order), int(bool(compact)), ptr(scratch), ptr(totals), st), "es_mesh_clean_count")
+        V2, T2, degenerate = (int(v) for v in totals.tolist())
+        verts_out, tris_out, vmap = self.empty(V2, 3), self.empty(T2, 3, dtype=torch.int32), self.empty(V2, dtype=torch.int64)
+        check(self.lib.es_mesh_keep_emit(ptr(v32), ptr(t32), V, T, ptr(scratch), V2, T2, ptr(verts_out), ptr(tris_out), ptr(vmap), st),
+              "es_mesh_keep_emit")
+        return verts_out, tris_out, vmap, {"degenerate": degenerate, "duplicates": T - degenerate - T2, "kept_triangles": T2}
+
+    def mesh_clean(self, vertices: torch.Tensor, triangles: torch.Tensor, compact: bool = False):
+        """The mesh without its degenerate and duplicate triangles (``meshing.mesh_clean`` is the numpy twin and the specification; what
+        Open3D's remove_degenerate_triangles + remove_duplicated_triangles do): a triangle with a repeated index goes, and of the
+        triangles with the same three vertex indices, in any rotation or orientation, the one with the smallest triangle index stays.
+        Survivors keep their order and their own orientation.  (verts [V', 3], tris [T', 3] int32, vertex_map [V'] int64, stats):
+        ``compact=True`` also drops the vertices no surviving triangle uses and renumbers, ``vertex_map`` being the old index of each
+        new vertex as in ``keep_components``; ``stats``: degenerate, duplicates, kept_triangles.  One read-back (three counts)."""
+        v32 = self._rows3_arg(vertices, "mesh_clean", "[V, 3] vertices")
+        t32, V, T = self._mesh_args(triangles, v32.shape[0], "mesh_clean")
+        return self._mesh_clean(v32, t32, V, T, compact)
+
+    def vertex_normals(self, vertices: torch.Tensor, triangles: torch.Tensor):
+        """Area-weighted vertex normals [V, 3] fp32 of a device mesh, bit for bit those of ``meshing.vertex_normals`` (the numpy twin
+        and the specification) for fp32 vertices: per vertex the fp64 sum of the un-normalised fp64 face cross products of its
+        triangles, added in the twin's order (corner 0 of every triangle in triangle order, then corner 1, then corner 2), normalised;
+        0 for a vertex of no triangle with an area.  No float atomics, no read-back."""
+        v32 = self._rows3_arg(vertices, "vertex_normals", "[V, 3] vertices")
+        t32, V, T = self._mesh_args(triangles, v32.shape[0], "vertex_normals")
+        st, scratch = self.st(), self._scratch("es_vn_scratch_bytes", V)
+        corner_vertex, normals = self.empty(3 * T, dtype=torch.int32), self.empty(V, 3)
+        check(self.lib.es_vn_count(ptr(t32), V, T, ptr(corner_vertex), ptr(scratch), st), "es_vn_count")
+        order = torch.sort(corner_vertex, stable=True).indices
+        check(self.lib.es_vn_gather(ptr(v32), ptr(t32), V, T, ptr(order), ptr(scratch), ptr(normals), st), "es_vn_gather")
+        return normals
+
+    def cluster_vertices(self, vertices: torch.Tensor, triangles: torch.Tensor, cell: float, origin=(0.0, 0.0, 0.0), attributes=None):
+        """Vertex clustering (``meshing.cluster_vertices`` is the numpy twin and the specification; the averaging variant of Open3D's
+        simplify_vertex_clustering): the vertices of one cell floor((float64(v) - origin) / cell) become one vertex, their fp64 mean in
+        ascending index rounded to fp32, numbered by ascending (ix, iy, iz); ``attributes`` [V, C <= 8] are averaged likewise; the
+        triangles are renumbered and cleaned (``mesh_clean``: collapsed and duplicate triangles go, order kept).  Cell coordinates must
+        lie in [-2^20, 2^20).  Returns (verts [V', 3], tris [T', 3] int32, attributes [V', C] or None, vertex_cluster [V] int32,
+        stats: cells, largest_cell, degenerate, duplicates, kept_triangles).  Two read-backs (the cell counts, the clean-up's)."""
+        from .meshing import RAST_MAX_ATTRS
+        v32 = self._rows3_arg(vertices, "cluster_vertices", "[V, 3] vertices")
+        t32, V, T = self._mesh_args(triangles, v32.shape[0], "cluster_vertices")
+        org = [float(o) for o in origin]
+        if len(org) != 3:
+            raise _lib.EndoSurfHipError(f"cluster_vertices: origin must have three entries (got {origin!r})")
+        att, Cn = None, 0
+        if attributes is not None:
+            if attributes.dim() != 2 or attributes.shape[0] != V or not 1 <= attributes.shape[1] <= RAST_MAX_ATTRS or attributes.device != self.device:
+                raise _lib.EndoSurfHipError(f"cluster_vertices takes [V, 1..{RAST_MAX_ATTRS}] attributes on {self.device} (got {tuple(attributes.shape)})")
+            att, Cn = f32(attributes), int(attributes.shape[1])
+        st, scratch = self.st(), self._scratch("es_cluster_scratch_bytes", V)
+        key = self.empty(V, dtype=torch.int64)
+        check(self.lib.es_cluster_keys(ptr(v32), V, float(cell), *org, ptr(key), st), "es_cluster_keys")
+        sorted_key, order = torch.sort(key, stable=True)
+        totals = self.empty(3, dtype=torch.int64)
+        check(self.lib.es_cluster_count(ptr(sorted_key), V, ptr(scratch), ptr(totals), st), "es_cluster_count")
+        cells, bad, largest = (int(v) for v in totals.tolist())
+        verts_out, cluster = self.empty(cells, 3), self.empty(V, dtype=torch.int32)
+        att_out = self.empty(cells, Cn) if Cn else None
+        check(self.lib.es_cluster_emit(ptr(v32), ptr(att), Cn, V, ptr(order), ptr(scratch), cells, bad, ptr(verts_out), ptr(att_out), ptr(cluster), st),
+              "es_cluster_emit")
+        remapped = self.empty(T, 3, dtype=torch.int32)
+        check(self.lib.es_cluster_remap(ptr(t32), V, T, ptr(cluster), ptr(remapped), st), "es_cluster_remap")
+        _, tris_out, _, cstats = self._mesh_clean(verts_out, remapped, cells, T, False)
+        return verts_out, tris_out, att_out, cluster, dict(cells=cells, largest_cell=largest, **cstats)
+
+    def ply_pack(self, vertices: torch.Tensor, triangles=None, colors=None, normals=None):
+        """The body of a ``binary_little_endian 1.0`` PLY file as a uint8 device tensor (``data.ply_body`` is the numpy twin, and
+        ``data.ply_header`` the text in front of it): per vertex ``float x y z``, then ``float nx ny nz`` with ``normals`` [V, 3], then
+        ``uchar red green blue`` with ``colors`` [V, 3] -- floats quantised by the rule of ``data.to8b``, trunc(255 clip(c, 0, 1)) in
+        fp32: below 0 gives 0, above 1 gives 255, NaN 0 --; then per triangle ``uchar 3`` and three ``int`` indices (13 bytes).
+        ``triangles=None`` packs a point cloud.  No read-back."""
+        v32 = self._rows3_arg(vertices, "ply_pack", "[V, 3] vertices")
+        V = int(v32.shape[0])
+        t32 = None if triangles is None else self._tri_arg(triangles, "ply_pack")
+        T = 0 if t32 is None else int(t32.shape[0])
+        rows = {}
+        for name, a in (("normals", normals), ("colors", colors)):
+            rows[name] = None
+            if a is not None:
+                rows[name] = self._rows3_arg(a, "ply_pack", f"[V, 3] {name}")
+                if rows[name].shape[0] != V:
+                    raise _lib.EndoSurfHipError(f"ply_pack: {name} has {rows[name].shape[0]} rows for {V} vertices")
+        out = self.empty(self._scratch_bytes("es_ply_body_bytes", V, T, int(normals is not None), int(colors is not None)), dtype=torch.uint8)
+        check(self.lib.es_ply_pack(ptr(v32), ptr(rows["normals"]), ptr(rows["colors"]), ptr(t32), V, T, ptr(out), self.st()), "es_ply_pack")
+        return out
+
     # ---- mesh rasteriser (csrc/raster.hip) ------------------------------------------------------------------------------
     def project_vertices(self, vertices: torch.Tensor, intrinsics, pose):
         """Stage A of the rasteriser (``meshing.project_vertices`` is the numpy twin and the specification): world vertices [V, 3]

@@ -507,3 +507,95 @@ def vertex_normals(vertices, triangles):
     for k in range(3):
         np.add.at(n, f[:, k], fn)
     return (n / np.maximum(np.linalg.norm(n, axis=1, keepdims=True), 1e-30)).astype(np.float32)
+
+
+# ---- mesh export: clean-up and vertex clustering (host twins of csrc/mesh.hip es_mesh_clean_* and csrc/export.hip) ------
+def _clean_keep(tri):
+    """(keep [T] bool, degenerate [T] bool) of checked int64 triangles: the rule of ``mesh_clean``."""
+    good = (tri[:, 0] != tri[:, 1]) & (tri[:, 1] != tri[:, 2]) & (tri[:, 0] != tri[:, 2])
+    keep = np.zeros(len(tri), bool)
+    ids = np.nonzero(good)[0]
+    if len(ids):
+        _, first = np.unique(np.sort(tri[ids], axis=1), axis=0, return_index=True)          # the first occurrence of each corner set
+        keep[ids[first]] = True
+    return keep, ~good
+
+
+def mesh_clean(vertices, triangles, compact=False):
+    """The mesh without its degenerate and duplicate triangles (numpy twin of ``Engine.mesh_clean``; what Open3D's
+    ``remove_degenerate_triangles`` and ``remove_duplicated_triangles`` do together).
+
+    A triangle with a repeated index is degenerate and goes.  Two triangles are duplicates when they name the same three vertices, in
+    any rotation and either orientation; of a set of duplicates the one with the smallest triangle index stays.  Surviving triangles
+    keep their input order and their own orientation.  ``compact=True`` also drops the vertices no surviving triangle uses and
+    renumbers; ``compact=False`` keeps every vertex.  Indices are compared as integers: nothing is folded for V, T < 2^31.
+    Returns (vertices [V', 3], triangles [T', 3] int32, vertex_map [V'] int64: the old index of each new vertex (the convention of
+    ``keep_components``), stats: degenerate, duplicates, kept_triangles)."""
+    verts = np.asarray(vertices)
+    if verts.ndim != 2 or verts.shape[1] != 3:
+        raise ValueError(f"vertices must be [V, 3] (got {verts.shape})")
+    tri, V = _as_triangles(triangles, len(verts))
+    keep, degenerate = _clean_keep(tri)
+    used = np.ones(V, bool)
+    if compact:
+        used = np.zeros(V, bool)
+        used[tri[keep].reshape(-1)] = True
+    vmap = np.nonzero(used)[0].astype(np.int64)
+    new_id = np.cumsum(used) - 1
+    n_deg, n_keep = int(degenerate.sum()), int(keep.sum())
+    stats = {"degenerate": n_deg, "duplicates": len(tri) - n_deg - n_keep, "kept_triangles": n_keep}
+    return verts[vmap], new_id[tri[keep]].astype(np.int32).reshape(-1, 3), vmap, stats
+
+
+CLUSTER_MAX_ATTRS = 8
+CLUSTER_HALF = 1 << 20               # cell coordinates lie in [-2^20, 2^20): three of them pack into one 63-bit key
+
+
+def cluster_vertices(vertices, triangles, cell, origin=(0.0, 0.0, 0.0), attributes=None):
+    """Vertex clustering (numpy twin of ``Engine.cluster_vertices``; the averaging variant of Open3D's ``simplify_vertex_clustering``).
+
+    The cell of a vertex is floor((float64(v) - origin) / cell) per axis (v the fp32 coordinate; one subtraction and one division in
+    fp64).  Every cell coordinate must lie in [-2^20, 2^20) -- ValueError otherwise, as for a vertex that is not finite.  Each occupied
+    cell becomes one vertex; cells are numbered by ascending (ix, iy, iz), ix most significant.  Its position is the fp64 sum of its
+    members' positions, added in ascending old index, divided by their number and rounded to fp32; ``attributes`` [V, C], 1 <= C <= 8
+    (colours, normals) are averaged the same way.  The triangles are renumbered and then cleaned by the rule of ``mesh_clean`` (a
+    triangle with two corners in one cell, and duplicates, go; order kept; every new vertex stays, used or not).
+    Returns (vertices [V', 3] float32, triangles [T', 3] int32, attributes [V', C] float32 or None, vertex_cluster [V] int32: the new
+    vertex of each old one, stats: cells, largest_cell, degenerate, duplicates, kept_triangles)."""
+    verts = np.ascontiguousarray(np.asarray(vertices, np.float32))
+    if verts.ndim != 2 or verts.shape[1] != 3:
+        raise ValueError(f"vertices must be [V, 3] (got {verts.shape})")
+    tri, V = _as_triangles(triangles, len(verts))
+    cell = float(cell)
+    org = np.asarray(origin, np.float64).reshape(-1)
+    if not (cell > 0.0 and np.isfinite(cell)) or org.shape != (3,) or not np.isfinite(org).all():
+        raise ValueError("cell must be finite and positive, origin three finite numbers")
+    att = None
+    if attributes is not None:
+        att = np.asarray(attributes, np.float32)
+        if att.ndim != 2 or att.shape[0] != V or not 1 <= att.shape[1] <= CLUSTER_MAX_ATTRS:
+            raise ValueError(f"attributes must be [V, 1..{CLUSTER_MAX_ATTRS}]")
+    with np.errstate(invalid="ignore", over="ignore"):
+        idx = np.floor((verts.astype(np.float64) - org[None]) / cell)
+    if not ((idx >= -CLUSTER_HALF) & (idx < CLUSTER_HALF)).all():          # (NaN fails both)
+        raise ValueError("a vertex's cell coordinate lies outside [-2^20, 2^20) (or the vertex is not finite): use a larger cell")
+    q = idx.astype(np.int64) + CLUSTER_HALF
+    key = (q[:, 0] << 42) | (q[:, 1] << 21) | q[:, 2]
+    order = np.argsort(key, kind="stable")                                   # by (cell, old index)
+    cells, cluster_sorted, counts = np.unique(key[order], return_inverse=True, return_counts=True)
+    cluster_sorted = cluster_sorted.reshape(-1)
+    n = len(cells)
+
+    def mean(x):          # np.add.at adds one row after the other, in the order given: ascending old index within a cell
+        acc = np.zeros((n, x.shape[1]), np.float64)
+        np.add.at(acc, cluster_sorted, x[order].astype(np.float64))
+        return (acc / counts[:, None].astype(np.float64)).astype(np.float32)
+
+    vertex_cluster = np.zeros(V, np.int64)
+    vertex_cluster[order] = cluster_sorted
+    keep, degenerate = _clean_keep(vertex_cluster[tri].reshape(-1, 3))
+    n_deg, n_keep = int(degenerate.sum()), int(keep.sum())
+    stats = {"cells": n, "largest_cell": int(counts.max()) if n else 0, "degenerate": n_deg, "duplicates": len(tri) - n_deg - n_keep,
+             "kept_triangles": n_keep}
+    return (mean(verts), vertex_cluster[tri[keep]].astype(np.int32).reshape(-1, 3), None if att is None else mean(att),
+            vertex_cluster.astype(np.int32), stats)

@@ -843,7 +843,7 @@ class EndoSurfRenderer(nn.Module):
 
     @_on_device
     def extract_observation_mesh(self, t, bound_min, bound_max, resolution, threshold=0.0, net_chunk=1 << 22, view_point=None, refine_steps=0,
-                                 band=None, components=None):
+                                 band=None, components=None, clean=False, simplify=None):
         """The observed-space surface at time t as a coloured mesh, device tensors only (what the reference's demo assembles from
         extract_observation_geometry + renderonpts, trainer_endosurf.py:403-460): ``vertices`` [V,3] world coordinates, ``triangles``
         [T,3] int32, ``normals`` [V,3] the analytic observed-space SDF gradient at the vertices normalised as renderonpts does, ``sdf``
@@ -870,7 +870,15 @@ class EndoSurfRenderer(nn.Module):
         (trainer_endosurf.py:440-445), by ``Engine.keep_components`` (csrc/mesh.hip): components by shared vertices, degenerate
         triangles dropped, order kept; ``compact=False`` keeps the orphaned vertices as the reference does.  Adds ``components`` (a dict
         of counts: components, max_triangles, kept_triangles, degenerate, rounds) to the result.  The filter removes exactly what a
-        too small band ``lipschitz`` can lose, so band and dense agree behind it.  The default ``None`` keeps every triangle."""
+        too small band ``lipschitz`` can lose, so band and dense agree behind it.  The default ``None`` keeps every triangle.
+
+        ``clean=True`` removes, after the component filter, every triangle with a repeated index and every duplicate of an earlier
+        triangle (``Engine.mesh_clean``; unreferenced vertices go as well) and adds ``clean`` (a dict of counts: degenerate, duplicates,
+        kept_triangles).  ``simplify=c`` (a cell size in scene units, cells counted from the origin) or ``simplify="grid"`` (one cell of
+        the extraction lattice, counted from ``bound_min``) then merges the vertices of each cell into their mean
+        (``Engine.cluster_vertices``, which cleans behind itself) before refinement, normals and colours, which are therefore evaluated
+        at the clustered vertices, not averaged; it adds ``simplify`` (cells, largest_cell, degenerate, duplicates, kept_triangles).
+        Both are off by default, and the mesh is then bit for bit what it was without these keywords."""
         comp = self._components_arg(components)
         if band is not None and band is not False:
             vertices, triangles, stats = self._mesh_on_device_band(t, bound_min, bound_max, resolution, threshold, net_chunk, band)
@@ -879,6 +887,12 @@ class EndoSurfRenderer(nn.Module):
         cstats = None
         if comp is not None:
             vertices, triangles, _, cstats = self.engine.keep_components(vertices, triangles, **comp)
+        clean_stats = simplify_stats = None
+        if clean:
+            vertices, triangles, _, clean_stats = self.engine.mesh_clean(vertices, triangles, compact=True)
+        if simplify is not None and simplify is not False:
+            cell, origin = self._simplify_arg(simplify, bound_min, bound_max, resolution)
+            vertices, triangles, _, _, simplify_stats = self.engine.cluster_vertices(vertices, triangles, cell, origin)
         tt = torch.as_tensor(t, dtype=torch.float32, device=self.device).reshape(-1)[:1]
         chunk = max(1, min(int(net_chunk), 1 << 17))
 
@@ -892,6 +906,10 @@ class EndoSurfRenderer(nn.Module):
             out["stats"] = stats
         if cstats is not None:
             out["components"] = cstats
+        if clean_stats is not None:
+            out["clean"] = clean_stats
+        if simplify_stats is not None:
+            out["simplify"] = simplify_stats
         if vertices.shape[0] == 0:
             out.update(normals=vertices.clone(), sdf=vertices.new_zeros(0))
             if view_point is not None:
@@ -916,6 +934,50 @@ class EndoSurfRenderer(nn.Module):
             s, _ = sdf_grad(vertices)
         out["sdf"] = s.reshape(-1)
         return out
+
+    @staticmethod
+    def _simplify_arg(simplify, bound_min, bound_max, resolution):
+        """The ``simplify`` keyword as (cell, origin) of Engine.cluster_vertices: a cell size in scene units counted from the origin, or
+        "grid": the largest spacing of the extraction lattice, counted from ``bound_min``."""
+        if isinstance(simplify, str):
+            if simplify != "grid":
+                raise ValueError(f'simplify takes a cell size or "grid" (got {simplify!r})')
+            bmin = torch.as_tensor(bound_min, dtype=torch.float32).cpu().double().reshape(3)
+            bmax = torch.as_tensor(bound_max, dtype=torch.float32).cpu().double().reshape(3)
+            return float(((bmax - bmin) / (float(resolution) - 1.0)).max()), tuple(float(b) for b in bmin)
+        cell = float(simplify)
+        if not cell > 0.0:
+            raise ValueError(f"simplify: the cell size must be positive (got {simplify!r})")
+        return cell, (0.0, 0.0, 0.0)
+
+    @_on_device
+    def export_observation_mesh(self, prefix, t, bound_min, bound_max, resolution, threshold=0.0, view_point=None, components=0.9, simplify=None,
+                                **extract_kwargs):
+        """The three mesh files of the reference's demo for one frame (trainer_endosurf.py:435-466), without Open3D:
+        ``prefix + "_geometry.ply"`` (vertices and triangles), ``prefix + "_color.ply"`` (plus the ``renderonpts`` colours clipped to
+        [0, 1]; white without a ``view_point``, as there is no direction to render from) and ``prefix + "_normal.ply"`` (plus the
+        paint (-n 0.5 + 0.5).clip(0, 1) of the normals ``Engine.vertex_normals`` computes from the triangles, the demo's
+        compute_vertex_normals).  The mesh is that of ``extract_observation_mesh`` with the component filter (``components``, 0.9 as in
+        the demo; None for none), always cleaned of degenerate and duplicate triangles, and clustered when ``simplify`` is given;
+        ``extract_kwargs`` (net_chunk, refine_steps, band) are passed on.  Files are ``data.write_ply``'s: binary little endian, fp32
+        coordinates, the body packed on the device, one copy to the host per file.  Returns the mesh dict with ``vertex_normals``
+        [V, 3] and ``paths`` (geometry, color, normal)."""
+        from .data import write_ply
+        unknown = set(extract_kwargs) - {"net_chunk", "refine_steps", "band"}
+        if unknown:
+            raise TypeError(f"export_observation_mesh passes net_chunk, refine_steps and band on (got {sorted(unknown)})")
+        mesh = self.extract_observation_mesh(t, bound_min, bound_max, resolution, threshold=threshold, view_point=view_point, components=components,
+                                             clean=True, simplify=simplify, **extract_kwargs)
+        v, f = mesh["vertices"], mesh["triangles"]
+        vn = self.engine.vertex_normals(v, f)
+        colors = mesh["colors"].clamp(0.0, 1.0) if "colors" in mesh else torch.ones_like(v)
+        prefix = str(prefix)
+        paths = {k: f"{prefix}_{k}.ply" for k in ("geometry", "color", "normal")}
+        write_ply(paths["geometry"], v, f, engine=self.engine)
+        write_ply(paths["color"], v, f, colors=colors, engine=self.engine)
+        write_ply(paths["normal"], v, f, colors=(-vn * 0.5 + 0.5).clamp(0.0, 1.0), engine=self.engine)
+        mesh.update(vertex_normals=vn, paths=paths)
+        return mesh
 
     @_on_device
     def geometric_error(self, mesh_or_vertices, depth, intrinsics, pose, depth_trunc, depth_scale=1.0) -> float:

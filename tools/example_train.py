@@ -124,7 +124,20 @@ def main():
                                    perturb_overwrite=False)
     write_png(os.path.join(args.out, "eval_000.png"), ev["sheet"][0])
     print(f"eval sheet 3200x512 (eval_000.png) in {time.perf_counter() - t1:.2f} s with the render: " + ", ".join(f"{k} {x:.4f}" for k, x in ev["stats"].items()))
-    assert np.isfinite(psnr) and len(v) > 0 and m["vertices"].shape[0] > 0
+    # the demo's 3D deliverable: NNN_geometry / _color / _normal.ply of the cleaned, grid-clustered mesh and NNN_gt.ply, the depth frame's
+    # point cloud with the frame's colours -- packed on the device, written without Open3D
+    from endosurf_amd.data import depth_points, read_ply, write_ply
+    t1 = time.perf_counter()
+    ex = renderer2.export_observation_mesh(os.path.join(args.out, "000"), torch.tensor([0.5]), [-1, -1, -1], [1, 1, 1], resolution=256,
+                                           view_point=[0.0, 0.0, -1.5], components=0.9, simplify="grid", band=True)
+    gt = depth_points(depth.to(dev), K, pose, 3.0)
+    write_ply(os.path.join(args.out, "000_gt.ply"), gt, colors=gt_color[0][(depth > 0).to(dev)], engine=renderer2.engine)
+    torch.cuda.synchronize()
+    back = read_ply(ex["paths"]["normal"])
+    print(f"mesh files 000_geometry / _color / _normal / _gt.ply in {time.perf_counter() - t1:.2f} s with the extraction: "
+          f"{back['triangles'].shape[0]} triangles of {m['triangles'].shape[0]} ({ex['simplify']['cells']} cells, {ex['clean']['duplicates']} duplicates "
+          f"and {ex['clean']['degenerate']} degenerate triangles removed before clustering), {gt.shape[0]} ground-truth points")
+    assert np.isfinite(psnr) and len(v) > 0 and m["vertices"].shape[0] > 0 and back["triangles"].shape[0] > 0
 
 
 if __name__ == "__main__":
