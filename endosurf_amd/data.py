@@ -264,6 +264,25 @@ def cal_geometric_error(points, vertices, depth_scale: float = 1.0, engine=None)
     return float(dist.astype(np.float64).mean()) * float(depth_scale) if dist.size else float("nan")
 
 
+def cal_surface_error(points, vertices, triangles, depth_scale: float = 1.0, engine=None) -> float:
+    """``cal_geometric_error`` measured to the surface instead of its vertices: the mean over ``points`` [M,3] of the exact distance to
+    the triangle mesh ``vertices`` [V,3] / ``triangles`` [T,3] (``point_to_mesh``: the closest point of the closest triangle), times
+    ``depth_scale``.  It does not depend on how finely the surface is tessellated.  Device tensors go through
+    ``engine.point_to_mesh`` (an ``Engine`` of their device is made when none is given), anything else through the numpy twin
+    ``meshing.point_to_mesh``.  nan for an empty cloud, inf for a mesh without a valid triangle."""
+    if all(torch.is_tensor(a) and a.is_cuda for a in (points, vertices, triangles)):
+        if engine is None:
+            from .engine import Engine
+            engine = Engine(points.device)
+        with torch.cuda.device(engine.device):
+            dist = engine.point_to_mesh(points, vertices, triangles)[0]
+        return float(dist.double().mean()) * float(depth_scale) if dist.numel() else float("nan")
+    from .meshing import point_to_mesh
+    as_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    dist = point_to_mesh(as_np(points), as_np(vertices), as_np(triangles))[0]
+    return float(dist.astype(np.float64).mean()) * float(depth_scale) if dist.size else float("nan")
+
+
 # ---- binary PLY files (the reference's demo writes its meshes through Open3D, trainer_endosurf.py:447-466; DESIGN.md 7e) ---------------
 PLY_VERTEX_PROPS = ("x", "y", "z")
 PLY_NORMAL_PROPS = ("nx", "ny", "nz")

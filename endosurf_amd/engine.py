@@ -790,6 +790,32 @@ class Engine:
         check(self.lib.es_nn_query(ptr(q), Q, P, ptr(scratch), ptr(dist), ptr(index), st), "es_nn_query")
         return dist, index
 
+    # ---- point-to-surface distance (csrc/surface.hip; contract: DESIGN.md 7f) ------------------------------------------------
+    def point_to_mesh(self, points: torch.Tensor, vertices: torch.Tensor, triangles: torch.Tensor, return_work: bool = False):
+        """Exact distance from each row of ``points`` [Q, 3] to the triangle mesh ``vertices`` [V, 3] / ``triangles`` [T, 3] (int32 or
+        int64), all on this device: (dist [Q] fp32, triangle [Q] int32, closest [Q, 3] fp32) by the rule of ``meshing.point_to_mesh``
+        (the numpy twin and the specification), evaluated in fp64.  A triangle with a repeated or out-of-range index or a non-finite
+        corner is skipped, not an error; inf / -1 / nan where there is no answer (a non-finite query row, no triangle that takes
+        part).  Bit-identical from call to call; no read-back.  ``return_work=True`` appends work [Q, 2] int32: the cell shells a
+        query read and the triangles it measured."""
+        q = self._rows3_arg(points, "point_to_mesh", "[N, 3] points")
+        v = self._rows3_arg(vertices, "point_to_mesh", "[N, 3] vertices")
+        if not torch.is_tensor(triangles) or triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.device != self.device \
+                or triangles.dtype not in (torch.int32, torch.int64):
+            raise _lib.EndoSurfHipError(f"point_to_mesh takes [T, 3] int32 / int64 triangles on {self.device}")
+        Q, V, T = int(q.shape[0]), int(v.shape[0]), int(triangles.shape[0])
+        t = triangles.detach()
+        if t.dtype == torch.int64:          # an index beyond int32 must stay out of range, not wrap into it
+            t = torch.where((t < 0) | (t >= V), torch.full_like(t, -1), t)
+        t32 = t.to(torch.int32).contiguous()
+        scratch, st = self._scratch("es_surf_scratch_bytes", V, T), self.st()
+        dist, tri, closest = self.empty(Q), self.empty(Q, dtype=torch.int32), self.empty(Q, 3)
+        work = self.empty(Q, 2, dtype=torch.int32) if return_work else None
+        check(self.lib.es_surf_build(ptr(v), ptr(t32), V, T, ptr(scratch), st), "es_surf_build")
+        check(self.lib.es_surf_query(ptr(q), Q, ptr(v), ptr(t32), V, T, ptr(scratch), ptr(dist), ptr(tri), ptr(closest), ptr(work), st),
+              "es_surf_query")
+        return (dist, tri, closest, work) if return_work else (dist, tri, closest)
+
     # ---- mesh export: clean-up, normals, clustering, PLY body (csrc/mesh.hip, csrc/export.hip; contract: DESIGN.md 7e) ------
     def _mesh_clean(self, v32, t32, V, T, compact):
         """``mesh_clean`` of checked arguments.  The two stable sorts order the triangles by (sorted corners, triangle index)."""

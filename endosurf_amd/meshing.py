@@ -299,6 +299,121 @@ def nearest(query, points, chunk=1 << 22):
     return np.sqrt(best), arg.astype(np.int32)
 
 
+# ---- point-to-surface distance (host twin of csrc/surface.hip; contract: DESIGN.md 7f) ------------------------------------------------
+def _dot3(a, b):          # vectors are tuples of three component arrays: no [..., 3] temporaries
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+def _cross3(a, b):
+    return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
+
+
+def _sub3(a, b):
+    return (a[0] - b[0], a[1] - b[1], a[2] - b[2])
+
+
+def _where3(c, a, b):
+    return tuple(np.where(c, x, y) for x, y in zip(a, b))
+
+
+def _surface_inputs(points, vertices, triangles):
+    """(queries [Q,3] fp32, vertices [V,3] fp32, triangles [T,3] int64, the indices of the triangles that take part)."""
+    q = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+    v = np.ascontiguousarray(np.asarray(vertices, np.float32).reshape(-1, 3))
+    tri = np.asarray(triangles)
+    if tri.size == 0:
+        tri = np.zeros((0, 3), np.int64)
+    if tri.ndim != 2 or tri.shape[1] != 3 or not np.issubdtype(tri.dtype, np.integer):
+        raise ValueError(f"triangles must be an integer [T, 3] array (got {tri.dtype} {tri.shape})")
+    if len(q) >= 1 << 31 or len(v) >= 1 << 31 or len(tri) >= 1 << 31:
+        raise ValueError("query / vertex / triangle counts must be below 2^31")
+    tri = tri.astype(np.int64)
+    ok = ((tri >= 0) & (tri < len(v))).all(axis=1) & (tri[:, 0] != tri[:, 1]) & (tri[:, 1] != tri[:, 2]) & (tri[:, 0] != tri[:, 2])
+    ids = np.nonzero(ok)[0]
+    ids = ids[np.isfinite(v[tri[ids]]).all(axis=(1, 2))] if len(ids) else ids
+    return q, v, tri, ids
+
+
+def _point_triangles(q, v, tri):
+    """(d2 [R,K] fp64, closest [R,K,3] fp64) of finite queries ``q`` [R,3] fp32 against the K triangles ``tri`` (all of them take part):
+    the per-triangle rule of ``point_to_mesh``."""
+    q = tuple(q[:, k].astype(np.float64)[:, None] for k in range(3))
+    i0, i1, i2 = (tri[:, k][None] for k in range(3))
+    v0, v1, v2 = (tuple(v[tri[:, j], k].astype(np.float64)[None] for k in range(3)) for j in range(3))
+    n = _cross3(_sub3(v1, v0), _sub3(v2, v0))
+    n2 = _dot3(n, n)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        s = _dot3(_sub3(q, v0), n) / n2
+        p = tuple(q[k] - s * n[k] for k in range(3))
+        inside = (n2 > 0) & (_dot3(_cross3(_sub3(v1, v0), _sub3(p, v0)), n) > 0) & (_dot3(_cross3(_sub3(v2, v1), _sub3(p, v1)), n) > 0) \
+            & (_dot3(_cross3(_sub3(v0, v2), _sub3(p, v2)), n) > 0)
+        d = _sub3(q, p)
+        best = np.where(inside, _dot3(d, d), np.inf)
+    at = _where3(inside, p, (np.nan, np.nan, np.nan))
+    for ia, ib, pa, pb in ((i0, i1, v0, v1), (i1, i2, v1, v2), (i2, i0, v2, v0)):
+        swap = ia > ib
+        a, b = _where3(swap, pb, pa), _where3(swap, pa, pb)          # from the smaller vertex index to the larger
+        e = _sub3(b, a)
+        l2 = _dot3(e, e)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = np.where(l2 > 0, _dot3(_sub3(q, a), e) / l2, 0.0)
+        c = tuple(np.where(t <= 0, a[k], np.where(t >= 1, b[k], a[k] + t * e[k])) for k in range(3))
+        d = _sub3(q, c)
+        d2 = _dot3(d, d)
+        upd = d2 < best                                                  # strict: on a tie the face, then the earlier edge
+        best = np.where(upd, d2, best)
+        at = _where3(upd, c, at)
+    return best, np.stack(at, -1)
+
+
+def point_to_mesh(points, vertices, triangles, chunk=1 << 17, return_d2=False):
+    """Exact distance from each row of ``points`` [Q,3] to the triangle mesh (``vertices`` [V,3], ``triangles`` [T,3] integers): numpy
+    twin of ``Engine.point_to_mesh`` and its specification (chunked brute force).  Returns (dist [Q] float32, triangle [Q] int32,
+    closest [Q,3] float32).  All arithmetic is fp64 on the inputs rounded to fp32; x.y = (x0 y0 + x1 y1) + x2 y2.
+
+    * A triangle takes part iff its three indices are distinct, all lie in [0, V), and its three corners are finite.  Any other is
+      skipped: never dereferenced, never an answer.
+    * Edge.  The closest point of a segment is computed with the segment oriented from its smaller vertex index a to its larger b:
+      l2 = |b - a|^2, t = ((q - a).(b - a)) / l2 if l2 > 0 else 0; t <= 0 gives a itself, t >= 1 gives b itself, otherwise
+      c = a + t (b - a); d2 = |q - c|^2.  Two triangles that share an edge or a vertex therefore compute bit-identical values for it:
+      a tie between them is an exact tie.
+    * Face.  n = (v1 - v0) x (v2 - v0), n2 = n.n.  Only if n2 > 0: s = ((q - v0).n) / n2, p = q - s n; p counts iff the three side
+      values ((vb - va) x (p - va)).n, for (va, vb) = (v0, v1), (v1, v2), (v2, v0), are all strictly positive (the border belongs to
+      the edges); d2 = |q - p|^2.  A zero-area triangle with distinct indices is therefore its three segments.
+    * Per triangle: the smallest d2 among the face, if it counts, and the three edges; on a tie the face wins, then the edges in the
+      order v0v1, v1v2, v2v0.
+    * Per query: the lexicographic minimum of (d2, triangle index) over the triangles that take part: the result does not depend on
+      any order of evaluation.
+    * dist = float32(sqrt(d2)), closest = that triangle's closest point rounded to float32.  A non-finite query row, T == 0 or no
+      triangle that takes part gives inf / -1 / nan; Q == 0 gives empty arrays.
+
+    ``chunk``: query-triangle pairs evaluated at a time (a few hundred bytes of temporaries each).  ``return_d2=True`` appends the dense
+    matrix the minimum is taken over, d2 [Q,T] fp64 (inf for a triangle that takes no part and for a non-finite query row): for small
+    inputs (tests, probes)."""
+    q, v, tri, ids = _surface_inputs(points, vertices, triangles)
+    Q = len(q)
+    dist = np.full(Q, np.inf, np.float32)
+    arg = np.full(Q, -1, np.int32)
+    closest = np.full((Q, 3), np.nan, np.float32)
+    dense = np.full((Q, len(tri)), np.inf) if return_d2 else None
+    rows = np.nonzero(np.isfinite(q).all(axis=1))[0]
+    if len(ids) == 0 or len(rows) == 0:
+        return (dist, arg, closest, dense) if return_d2 else (dist, arg, closest)
+    tk = tri[ids]
+    step = max(1, int(chunk) // len(ids))
+    for r0 in range(0, len(rows), step):
+        r = rows[r0:r0 + step]
+        d2, at = _point_triangles(q[r], v, tk)
+        k = np.argmin(d2, axis=1)                    # the first minimum: ``ids`` ascends
+        j = np.arange(len(r))
+        dist[r] = np.sqrt(d2[j, k]).astype(np.float32)
+        arg[r] = ids[k]
+        closest[r] = at[j, k].astype(np.float32)
+        if return_d2:
+            dense[np.ix_(r, ids)] = d2
+    return (dist, arg, closest, dense) if return_d2 else (dist, arg, closest)
+
+
 # ---- mesh rasteriser (host twins of csrc/raster.hip; contract: DESIGN.md 7c) ---------------------------------------------------------
 RAST_SUBPIXEL = 256                  # fixed-point units per pixel
 RAST_GUARD = 1 << 22                 # |fixed-point coordinate| <= this: every edge function fits in int64 with room to spare

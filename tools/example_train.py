@@ -94,9 +94,12 @@ def main():
     disc = b * b - a * cc
     depth = torch.where(disc > 0, (-b - disc.clamp_min(0).sqrt()) / a, torch.zeros_like(b))
     err = renderer2.geometric_error(clean, depth, K, pose, depth_trunc=3.0)
+    # ... and the same cloud against the mesh's surface (the closest point of the closest triangle): it does not move with the tessellation
+    surf = renderer2.surface_error(clean, depth, K, pose, depth_trunc=3.0, thresholds=(0.01,))
     cs = clean["components"]
     print(f"cleaned mesh: {cs['kept_triangles']} of {m['triangles'].shape[0]} triangles in the largest of {cs['components']} components "
-          f"({cs['rounds']} rounds); geometric error against the scene's depth frame: {err:.4f}")
+          f"({cs['rounds']} rounds); geometric error against the scene's depth frame: {err:.4f} (to the vertices), "
+          f"{surf['mean']:.4f} (to the surface; rmse {surf['rmse']:.4f}, {100.0 * surf['within'][0]:.1f} % within 0.01)")
     # the demo's "Mesh / Texture / Normal" panels of that mesh, without a display: rasterised once on the device, shaded three times
     clean = renderer2.extract_observation_mesh(torch.tensor([0.5]), [-1, -1, -1], [1, 1, 1], resolution=256, view_point=[0.0, 0.0, -1.5], band=True,
                                                components=0.9)
