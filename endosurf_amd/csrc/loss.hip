@@ -120,7 +120,7 @@ __global__ __launch_bounds__(1024) void k_train_loss(LossArgs a) {
 }
 
 int train_loss(const LossArgs& a, hipStream_t st) {
-    if (a.N <= 0) return ST_OK;
+    ES_REQUIRE(a.N >= 0, "train_loss: negative ray count");      // N == 0 launches: every sum is 0, the terms and normalisers are defined
     hipLaunchKernelGGL(k_train_loss, dim3(1), dim3(1024), 0, st, a);
     return hip_last("train_loss");
 }

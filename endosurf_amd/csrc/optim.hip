@@ -1,6 +1,10 @@
 // Adam (torch.optim.Adam defaults as used by the reference trainer, trainer_endosurf.py:70: betas (0.9, 0.999), eps 1e-8, no
 // weight decay / amsgrad) over the flat parameter buffer in ONE launch: 1.65 M parameters = 46 MB of HBM traffic (~10 us)
 // instead of the multi-tensor path's three launches over 82 small tensors (~0.23 ms).
+// WHICH Adam: beta1 and beta2 arrive as ``float`` and 1 - beta is formed from the rounded value (exact in fp32), so this is an exact Adam
+// with beta2 = fl32(0.999) = 0.99900001287..., whose two coefficients sum to 1.  torch.optim.Adam rounds beta2 and 1 - beta2 to fp32
+// separately.  The two differ by |fl32(b2) - b2| / (1 - b2) = 1.29e-5 relative in exp_avg_sq and by half of that, 6.7e-6 (measured,
+// tests/test_step_ref_host.py), of the update: harmless, but a reference with double betas cannot carry a gate tighter than that.
 #include <hip/hip_runtime.h>
 
 #include "launch.h"

@@ -234,7 +234,12 @@ class FlatAdam:
     """torch.optim.Adam with the reference's settings (trainer_endosurf.py:65-71: one group, defaults) as ONE kernel launch over
     the renderer's flat parameter buffer (es_adam_step).  The gradient is the flat buffer produced by es_weightnorm_backward
     (the parameters' ``.grad`` are views of it) plus the scalar variance gradient; if gradients were accumulated or produced
-    some other way they are gathered from ``.grad`` first.  ``param_groups[0]['lr']`` is read at every step like torch's."""
+    some other way they are gathered from ``.grad`` first.  ``param_groups[0]['lr']`` is read at every step like torch's.
+
+    Which Adam: the kernel takes the betas as fp32 and forms 1 - beta from the rounded value, i.e. it is an exact Adam with
+    beta2 = fl32(0.999) = 0.99900001287...; torch.optim.Adam rounds beta2 and 1 - beta2 separately.  Measured distance to Adam with
+    double betas: 1.29e-5 relative in ``exp_avg_sq``, 6.7e-6 of the update (tests/test_step_ref_host.py); the bias corrections are
+    computed on the host in double from the unrounded betas, like torch's."""
 
     def __init__(self, renderer, lr: float = 5e-4, betas=(0.9, 0.999), eps: float = 1e-8):
         self.model, self.eng = renderer.model, renderer.engine

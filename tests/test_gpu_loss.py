@@ -3,24 +3,9 @@ trainer_endosurf.py:133-162, endosurf.py:306-315, :337-339): values and gradient
 import pytest
 import torch
 
+from step_ref import torch_loss as _torch_loss          # the same formula carries the fp64 reference of test_gpu_step_kernels.py
+
 pytestmark = pytest.mark.gpu
-
-
-def _torch_loss(color_map, depth_map, eik, a_sdf, a_go, rays, eod_pts, color_gt, depth_gt, mask, cmask, valid_sn, w):
-    N = rays.shape[0]
-    color_loss = ((color_map - color_gt) * cmask).abs().sum() / (cmask.sum() + 1e-10)
-    cos = (rays[:, 3:6] * a_go[:N]).sum(-1, keepdim=True)
-    inside = (torch.linalg.norm(eod_pts, dim=-1, keepdim=True) < 1.0).float() * mask
-    den = inside.sum() + 1e-6
-    sdf_loss = (inside * a_sdf[:N]).abs().sum() / den
-    angle_loss = torch.relu(cos).abs().sum() / den
-    depth_loss = ((depth_map - depth_gt) * inside * mask).abs().sum() / ((inside * mask).sum() + 1e-10)
-    g = a_go[N:]
-    normal = g / (torch.linalg.norm(g, dim=-1, keepdim=True) + 1e-10)
-    diff = (normal[:N] - normal[N:]).abs() * valid_sn[:, None].float()
-    sn = diff.sum() / torch.clamp(valid_sn.sum() * 3, min=1).float()
-    terms = dict(color=color_loss, depth=depth_loss, sdf=sdf_loss, angle=angle_loss, eikonal=eik, surf_neig=sn)
-    return sum(w[k] * terms[k] for k in terms), terms
 
 
 @pytest.mark.parametrize("N,p_valid", [(1024, 0.7), (37, 0.5), (5000, 0.0)])

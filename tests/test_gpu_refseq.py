@@ -3,6 +3,8 @@
 points are evaluated into the tail of the live render's workspace and back-propagated by the render's ONE backward chain
 (renderer._Tail).  Same values, same gradients as the stand-alone evaluations -- whatever subset of the three results the loss uses,
 when the tail overflows, and when nobody claims it."""
+import math
+
 import pytest
 import torch
 
@@ -229,6 +231,25 @@ def test_reference_sequence_edge_batches(n):
     if n >= 1:
         assert r._live_tail is not None and r._live_tail[0].used > 0
         assert got[0][:2] == got[1][:2]
+
+
+def test_fused_loss_on_an_empty_batch():
+    """compute_loss_fused on an empty batch: es_train_loss launches for N == 0 like es_eod_loss / es_sn_loss do, so the total is the
+    formula's value, w_eik * eik (the five batch terms are 0 / eps = 0), not whatever the output buffers held."""
+    import weightgen
+    from gpu_util import renderer_for
+    from endosurf_amd.trainer import LOSS_WEIGHTS, compute_loss_fused
+    r = renderer_for(31, "trained", True)
+    batch = dict(rays=torch.from_numpy(weightgen.make_rays(5, 1)[:0]).cuda(),
+                 **{k: torch.from_numpy(v[:0]).cuda() for k, v in weightgen.make_targets(6, 1).items()})
+    for _ in range(2):          # (twice: the second call's output buffers are recycled, non-zero memory)
+        total, terms, ret = compute_loss_fused(r, batch, 3)
+        torch.cuda.synchronize()
+        want = torch.tensor(LOSS_WEIGHTS["eikonal"], dtype=torch.float32) * ret["gradient_o_error"].detach().cpu().reshape(())
+        got = float(total.detach())
+        assert math.isfinite(got) and got == float(want), (got, float(want))
+        assert [float(terms[k]) for k in ("color", "depth", "sdf", "angle", "surf_neig")] == [0.0] * 5
+        torch.full((4096,), float("nan"), device="cuda")          # leave poison where the next call's small buffers will land
 
 
 def test_deferred_errorondepth_semantics():
