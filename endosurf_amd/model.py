@@ -194,6 +194,8 @@ class EndoSurfNet(nn.Module):
     def __init__(self, net_cfg: dict, device):
         super().__init__()
         _check_arch(net_cfg)
+        self._renderer = self._pack_cache = self._flat_grad = None          # (_renderer: a weakref, set by the EndoSurfRenderer that owns the model)
+        self._epoch = 0            # bumped by in-place updates that bypass torch's version counters (trainer.FlatAdam)
         self.bound = net_cfg["bound"]
         self.use_deform = bool(net_cfg["use_deform"])
         lay = P.layout()
@@ -266,7 +268,7 @@ class EndoSurfNet(nn.Module):
                 off, shape = self._layout[key]
                 p.data = self._flat[off:off + max(1, int(np.prod(shape)))].view(tuple(shape))
         self._pack_cache = None
-        self._epoch = getattr(self, "_epoch", 0) + 1
+        self._epoch += 1
 
     def _apply(self, fn, recurse=True):
         """``.to() / .cuda() / .float()``: move the FLAT buffer and rebuild the parameter views (nn.Module._apply would give
@@ -312,7 +314,7 @@ class EndoSurfNet(nn.Module):
     # reference's are: the sdf query (its derivative IS g_o), the two gradient queries (second order: es_point_vjp) and forward() (position,
     # view direction and time: _NetForwardFn).
     def _r(self):
-        r = self._renderer() if getattr(self, "_renderer", None) is not None else None
+        r = self._renderer() if self._renderer is not None else None
         if r is None:
             raise RuntimeError("this EndoSurfNet is not attached to an EndoSurfRenderer")
         return r

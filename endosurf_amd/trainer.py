@@ -46,7 +46,7 @@ def compute_loss_fused(renderer, batch: Dict[str, torch.Tensor], iter_step: int,
     if need_p or need_n:
         # the step's random draws (stratified jitter [N], neighbour offsets [N,3]) in ONE library launch instead of two torch.rand's;
         # in a captured step the device-resident step counter selects the subsequence (Trainer.train_step_graph)
-        u4 = eng.uniform(4 * N, getattr(renderer, "_rng_step_dev", None))
+        u4 = eng.uniform(4 * N, renderer._rng_step_dev)
         if need_p:
             u_perturb = u4[:N]
         if need_n:
@@ -56,7 +56,7 @@ def compute_loss_fused(renderer, batch: Dict[str, torch.Tensor], iter_step: int,
     # (coarse query + 3 dependent 8-sample queries) are independent chains of small, latency-bound launches: run the sampling
     # on a side stream WHILE the main stream iterates the secant (two throughput-bound kernels would only slow each other)
     main = torch.cuda.current_stream(rays.device)
-    side = getattr(renderer, "_side_stream", None)
+    side = renderer._side_stream
     if side is None:
         side = renderer._side_stream = torch.cuda.Stream(device=rays.device)
     # (starting the sampling chain together with the marching query, or on a high-priority stream, was measured and is slower: DESIGN 4)
@@ -399,6 +399,7 @@ class Trainer:
         # (_pipeline_hook).  Same sums, same update; no multi-GPU box has measured it yet, so the default stays one bucket.
         self.overlap_allreduce = bool(overlap_allreduce)
         self._ar_stream = None
+        self._graph = self._plan = None          # train_step_graph's captured step; the buckets of the pipelined all-reduce (_bucket_plan)
         self.pipelined_steps = 0            # steps whose gradient really went through the bucket pipeline (not its one-bucket fallback)
         if self.exact_denominators:
             if schedule != "fused":
@@ -457,7 +458,7 @@ class Trainer:
         if not isinstance(opt, FlatAdam) or self.loss_fn is not compute_loss_fused:
             raise ValueError("train_step_graph needs the fused schedule and FlatAdam (the defaults; exact_denominators puts a collective "
                              "into the forward pass and is not captured)")
-        g = getattr(self, "_graph", None)
+        g = self._graph
         key = self._graph_key(batch, global_step)
         if g is None or g["key"] != key:
             scal = r.engine.zeros(4)          # step_size, bc2_sqrt, grad_scale | cos_anneal: written by es_train_schedule inside the step
@@ -551,7 +552,7 @@ class Trainer:
           A  deform layers 0..7   complete behind the deform launch   (side stream, under the sdf + colour launches)
           B  sdf                  complete behind the sdf launch      (side stream, under the colour launch)
           C  deform layer 8, colour, variance                         (main stream, after the backward: exposed)"""
-        plan = getattr(self, "_plan", None)
+        plan = self._plan
         if plan is None:
             from . import params as P
             m = self.renderer.model
