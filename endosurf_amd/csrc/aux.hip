@@ -7,6 +7,7 @@
 // form of the same arithmetic (loss.hip k_train_loss, rays.hip k_train_aux_points); the formulas here are the same ones.
 #include <hip/hip_runtime.h>
 
+#include "host.h"
 #include "launch.h"
 
 namespace es {

@@ -15,6 +15,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
+#include "../../include/endosurf_hip.h"
 #include "arch.h"
 
 namespace es {
@@ -406,15 +409,9 @@ __device__ __forceinline__ float smalln_reduce(const float* scr, int i, int row)
 //         dir = rays[ray][3:6]   (reference endosurf.py:66, 87, 153)
 // mode 2: the first M_split points are ray samples (as mode 1), the remaining M - M_split are explicit (x, t) without dirs:
 //         lets the training step evaluate its auxiliary points (errorondepth / surface neighbours) in the render launch
-struct PointSrc {
-    const float* x;
-    const float* t;
-    const float* dirs;
-    const float* rays;
-    const float* z;
-    int mode, t_scalar, n_per_ray, ldz;
-    int M, M_split;
-};
+// The public struct itself (fields: es_points in include/endosurf_hip.h), under the name the kernels take it by.
+struct PointSrc : ::es_points {};
+static_assert(sizeof(PointSrc) == sizeof(es_points) && std::is_standard_layout<PointSrc>::value, "es::PointSrc is es_points");
 __device__ __forceinline__ void load_point(const PointSrc& s, int i_in, float (&x)[3], float& t, float (&d)[3]) {
     int i = i_in;
     if (i >= s.M) { x[0] = x[1] = x[2] = 0.f; t = 0.f; d[0] = d[1] = 0.f; d[2] = 1.f; return; }

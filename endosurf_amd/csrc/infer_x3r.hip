@@ -9,6 +9,7 @@
 //   k_deform_vjp_x3r   reverse sweep for the covector g_c: g_o = J^T g_c = g_c + E(x)^T W_0^T M_0 W_1^T ... M_7 W_8^T g_c
 //                      (get_sdf_grad_from_observed_space, endosurf.py:581-601, is this product); a wave owns 32 points.
 #include "chain_common.h"
+#include "host.h"
 #include "launch.h"
 #include "x3r_core.h"
 #include "tabs.h"

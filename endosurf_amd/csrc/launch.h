@@ -80,6 +80,4 @@ struct DeviceOnce {
     void done() { mask[dev >> 6] |= 1ull << (dev & 63); }
 };
 
-int init_tables();
-
 }  // namespace es

@@ -4,8 +4,8 @@
 // batch sums, pass 2 (after a block barrier) writes the six loss terms and all adjoints (for d total = 1).
 #include <hip/hip_runtime.h>
 
+#include "host.h"
 #include "launch.h"
-#include "loss_args.h"
 
 namespace es {
 

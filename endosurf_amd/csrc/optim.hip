@@ -7,6 +7,7 @@
 // tests/test_step_ref_host.py), of the update: harmless, but a reference with double betas cannot carry a gate tighter than that.
 #include <hip/hip_runtime.h>
 
+#include "host.h"
 #include "launch.h"
 
 namespace es {

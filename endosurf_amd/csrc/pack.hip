@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "arch.h"
+#include "host.h"
 #include "launch.h"
 
 namespace es {

@@ -13,6 +13,7 @@
 
 #include "chain_common.h"
 #include "encode.h"
+#include "host.h"
 #include "launch.h"
 #include "tabs.h"
 #include "timing.h"
@@ -60,20 +61,19 @@ static int launch_bwd(const BwdArgs& a, int n0, int t0, int n1, int t1, hipStrea
     return ST_OK;
 }
 
-// train_x3r.hip
-int deform_tan_x3r(const PointSrc& src, const void* packed_r, const float* weff, float* ws, const WsLayout& L, const float* d_go, hipStream_t st, int m_rows = 0);
-int deform_bwd_x3r_with_tail(const BwdArgs& ba, const void* packed_r, int m_main, hipStream_t st);
-int color_bwd_x3r(const PointSrc& src, const void* packed_r, const float* weff, float* ws, const WsLayout& L, bool deform, int m_color, const float* d_rgb,
-                  hipStream_t st);
-int deform_bwd_x3r(const void* packed_r, const float* weff, float* ws, const WsLayout& L, int M, int m_color, hipStream_t st);
+// The argument block of a call's launches (as fwd_args of point_fwd.hip, with the incoming adjoints).
+static BwdArgs bwd_args(const PointSrc& src, const float* packed, const float* weff, float* ws, int flags, int M_color, const float* d_sdf,
+                        const float* d_go, const float* d_rgb) {
+    BwdArgs a;
+    a.src = src; a.tb = make_tabs(); a.packed = reinterpret_cast<const float4*>(packed); a.weff = weff; a.ws = ws;
+    a.L = ws_layout(src.M, flags); a.flags = flags; a.M_color = M_color; a.d_sdf = d_sdf; a.d_go = d_go; a.d_rgb = d_rgb;
+    return a;
+}
 
 int point_backward_chains(const PointSrc& src, const float* packed, const float* weff, float* ws, int flags, int m_color,
                           const float* d_sdf, const float* d_go, const float* d_rgb, hipStream_t st, const void* packed_x3) {
     if (src.M <= 0) return ST_OK;
-    BwdArgs a;
-    a.src = src; a.tb = make_tabs(); a.packed = reinterpret_cast<const float4*>(packed); a.weff = weff; a.ws = ws;
-    a.L = ws_layout(src.M, flags); a.flags = flags; a.d_sdf = d_sdf; a.d_go = d_go; a.d_rgb = d_rgb;
-    a.M_color = (flags & PF_COLOR) ? (m_color > 0 ? m_color : src.M) : 0;
+    const BwdArgs a = bwd_args(src, packed, weff, ws, flags, color_points(flags, m_color, src.M), d_sdf, d_go, d_rgb);
     const int Mp = a.L.Mp, Mcp = round_up64(a.M_color);
     const bool deform = flags & PF_DEFORM;
     if (flags & PF_X3_CHAIN) {

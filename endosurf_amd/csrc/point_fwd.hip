@@ -9,6 +9,7 @@
 // With PF_SAVE the layer inputs / reverse adjoints are streamed to the workspace for the backward pass.
 #include "chain_common.h"
 #include "encode.h"
+#include "host.h"
 #include "launch.h"
 #include "tabs.h"
 #include "timing.h"
@@ -62,23 +63,21 @@ static int launch_fwd(const FwdArgs& a, int n0, int t0, int n1, int t1, hipStrea
     return ST_OK;
 }
 
-// -------------------------------------------------------------------------------------------------------------
-// infer_x3r.hip
-int deform_jvp_x3r(const PointSrc& src, const void* packed_r, const float* weff, float* ws, const WsLayout& L, bool save, hipStream_t st);
-int deform_vjp_x3r(const PointSrc& src, const void* packed_r, const float* weff, float* ws, const WsLayout& L, bool save, hipStream_t st, int m_rows = 0);
-int deform_jvp_x3r_with_tail(const FwdArgs& fa, const void* packed_r, int m_main, hipStream_t st);
-int sdf_fwd_x3r(const PointSrc& src, const void* packed_r, const float* weff, float* ws, const WsLayout& L, bool deform, bool color, hipStream_t st);
-int color_fwd_x3r(const PointSrc& src, const void* packed_r, const float* weff, float* ws, const WsLayout& L, bool deform, int Mcp, bool save, hipStream_t st);
+// The argument block of a call's launches: the workspace is laid out for ``layout_flags``, the kernels see ``flags``; points
+// [0, M_color) go through the colour network.
+static FwdArgs fwd_args(const PointSrc& src, const float* packed, const float* weff, float* ws, int layout_flags, int flags, int M_color) {
+    FwdArgs a;
+    a.src = src; a.tb = make_tabs(); a.packed = reinterpret_cast<const float4*>(packed); a.weff = weff; a.ws = ws;
+    a.L = ws_layout(src.M, layout_flags); a.flags = flags; a.M_color = M_color;
+    return a;
+}
 
 // packed_x3 (nullable): the split weights of es_pack_x3; with PF_X3 and without PF_SAVE the deformation- and SDF-network launches of a
 // no-grad evaluation run in split precision (opt-in)
 int point_forward(const PointSrc& src, const float* packed, const float* weff, float* ws, int flags, int m_color, hipStream_t st,
                   const void* packed_x3) {
     if (src.M <= 0) return ST_OK;
-    FwdArgs a;
-    a.src = src; a.tb = make_tabs(); a.packed = reinterpret_cast<const float4*>(packed); a.weff = weff; a.ws = ws;
-    a.L = ws_layout(src.M, flags); a.flags = flags;
-    a.M_color = (flags & PF_COLOR) ? (m_color > 0 ? m_color : src.M) : 0;
+    const FwdArgs a = fwd_args(src, packed, weff, ws, flags, flags, color_points(flags, m_color, src.M));
     const int Mp = a.L.Mp, Mcp = round_up64(a.M_color);
     const bool deform = flags & PF_DEFORM;
     if ((flags & PF_X3) && !(flags & PF_SAVE) && packed_x3) {
@@ -151,10 +150,7 @@ int point_forward(const PointSrc& src, const float* packed, const float* weff, f
 int point_forward_rows(const PointSrc& src, const float* packed, const float* weff, float* ws, int flags, int m_color, int row0, int nrows,
                        hipStream_t st) {
     if (src.M <= 0 || nrows <= 0) return ST_OK;
-    FwdArgs a;
-    a.src = src; a.tb = make_tabs(); a.packed = reinterpret_cast<const float4*>(packed); a.weff = weff; a.ws = ws;
-    a.L = ws_layout(src.M, flags); a.flags = flags;
-    a.M_color = (flags & PF_COLOR) ? (m_color > 0 ? m_color : src.M) : 0;
+    const FwdArgs a = fwd_args(src, packed, weff, ws, flags, flags, color_points(flags, m_color, src.M));
     const int Mc = a.M_color;
     const bool deform = flags & PF_DEFORM;
     if (row0 + nrows > a.L.Mp) return fail(ST_BAD_ARG, "point_forward_rows", "rows beyond the workspace");
@@ -182,10 +178,7 @@ int point_forward_rows(const PointSrc& src, const float* packed, const float* we
 // against the same adjoint.  Nothing is saved (PF_SAVE is ignored: the forward's saved VJP adjoints stay as they are).
 int point_vjp(const PointSrc& src, const float* packed, const float* weff, float* ws, int flags, hipStream_t st) {
     if (src.M <= 0) return ST_OK;
-    FwdArgs a;
-    a.src = src; a.tb = make_tabs(); a.packed = reinterpret_cast<const float4*>(packed); a.weff = weff; a.ws = ws;
-    a.L = ws_layout(src.M, flags); a.flags = flags & ~PF_SAVE;
-    a.M_color = 0;
+    const FwdArgs a = fwd_args(src, packed, weff, ws, flags, flags & ~PF_SAVE, 0);
     ScopedTimer tm(KID_DEFORM_VJP, src.M, st);
     if (int e = launch_fwd<FB_NONE, FB_VJP>(a, 0, 0, a.L.Mp / TM, 0, st)) return e;
     return hip_last("point_vjp");
@@ -197,10 +190,7 @@ int point_vjp(const PointSrc& src, const float* packed, const float* weff, float
 // the colour network itself does not).  rgb -> WS_RGB.
 int color_forward(const PointSrc& src, const float* packed, const float* weff, float* ws, hipStream_t st) {
     if (src.M <= 0) return ST_OK;
-    FwdArgs a;
-    a.src = src; a.tb = make_tabs(); a.packed = reinterpret_cast<const float4*>(packed); a.weff = weff; a.ws = ws;
-    a.flags = PF_COLOR | PF_RAW_DIR;
-    a.L = ws_layout(src.M, PF_COLOR); a.M_color = src.M;
+    const FwdArgs a = fwd_args(src, packed, weff, ws, PF_COLOR, PF_COLOR | PF_RAW_DIR, src.M);
     ScopedTimer tm(KID_COLOR_FWD, src.M, st);
     if (int e = launch_fwd<FB_NONE, FB_COLOR>(a, 0, 0, a.L.Mp / TM, 0, st)) return e;
     return hip_last("color_forward");

@@ -5,6 +5,7 @@
 // workgroups.  16 rows x 256 columns per workgroup = 8 192 cycles per layer, 4x more workgroups than the 64-point kernel.
 // Weights come from the 16x16x4 packing appended to the packed buffer (arch.h P16_SEGS).
 #include "chain_common.h"
+#include "host.h"
 #include "launch.h"
 #include "tabs.h"
 #include "timing.h"

@@ -23,6 +23,7 @@
 // One workgroup = 256 threads = 4 waves = 128 points.  Both accumulator sets (previous layer / this layer) live in registers: ~400 of
 // the 512 per lane that a one-wave-per-SIMD kernel may use.
 #include "chain_common.h"
+#include "host.h"
 #include "launch.h"
 #include "x3r_core.h"
 #include "tabs.h"

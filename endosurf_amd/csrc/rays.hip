@@ -10,8 +10,8 @@
 //   march_find / secant_update  ray_marching + secant (endosurf.py:344-449), fixed-shape, no host branches
 #include <hip/hip_runtime.h>
 
+#include "host.h"
 #include "launch.h"
-#include "ray_args.h"
 
 namespace es {
 

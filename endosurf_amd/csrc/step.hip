@@ -7,6 +7,7 @@
 
 #include <cstdint>
 
+#include "host.h"
 #include "launch.h"
 
 namespace es {

@@ -11,6 +11,7 @@
 //                      (deform_bwd_tile): abar_7 = M_7 (W_8^T abar_8), abar_{l-1} = M_{l-1} (W_l^T abar_l); abar_0 .. abar_7 are kept
 //                      (WS_D_A, 2 rows per point like WS_D_U).  A wave owns 16 points = 32 columns.
 #include "chain_common.h"
+#include "host.h"
 #include "launch.h"
 #include "x3r_core.h"
 #include "tabs.h"

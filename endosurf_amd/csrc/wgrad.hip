@@ -15,6 +15,7 @@
 
 #include "arch.h"
 #include "chain_common.h"
+#include "host.h"
 #include "launch.h"
 #include "tabs.h"
 #include "timing.h"

@@ -18,15 +18,20 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "../../include/endosurf_hip.h"
+
 namespace es {
 
-constexpr int PF_DEFORM = 1;   // deformation network present (use_deform)
-constexpr int PF_COLOR = 2;    // evaluate the colour network (render_core) — off for errorondepth / surface_neighbour_error
-constexpr int PF_SAVE = 4;     // keep activations for the backward pass (training)
-constexpr int PF_X3_CHAIN = 32; // OPT-IN: the workspace belongs to the split-precision TRAINING chain (infer_x3r.hip with SAVE / train_x3r.hip): its
+// the public flags (include/endosurf_hip.h), under the names the kernels use
+constexpr int PF_DEFORM = ES_PF_DEFORM;   // deformation network present (use_deform)
+constexpr int PF_COLOR = ES_PF_COLOR;     // evaluate the colour network (render_core) — off for errorondepth / surface_neighbour_error
+constexpr int PF_SAVE = ES_PF_SAVE;       // keep activations for the backward pass (training)
+constexpr int PF_X3_CHAIN = ES_PF_X3_CHAIN; // OPT-IN: the workspace belongs to the split-precision TRAINING chain (infer_x3r.hip with SAVE / train_x3r.hip): its
                                 // ReLU mask words are in that family's layout, so the backward must run that family's kernels.  No effect on offsets
-constexpr int PF_RAW_DIR = 16;  // colour-only evaluation on explicit inputs (es_color_forward): the view direction is used as given, not normalised
-constexpr int PF_X3 = 8;       // OPT-IN: weight-gradient GEMMs in split precision (3 x bf16 planes, wgrad.hip); no effect on layouts
+constexpr int PF_X3 = ES_PF_X3;           // OPT-IN: weight-gradient GEMMs in split precision (3 x bf16 planes, wgrad.hip); no effect on layouts
+// internal only: colour-only evaluation on explicit inputs (es_color_forward): the view direction is used as given, not normalised
+constexpr int PF_RAW_DIR = 16;
+static_assert(!(PF_RAW_DIR & (ES_PF_DEFORM | ES_PF_COLOR | ES_PF_SAVE | ES_PF_X3 | ES_PF_X3_CHAIN)), "PF_RAW_DIR must stay clear of every public ES_PF_* flag");
 
 enum WsBuf : int {
     // forward outputs
@@ -66,8 +71,9 @@ enum WsBuf : int {
     WS_TBAR,       // [Mp]     the VJP sweep's adjoint of the TIME input: <c, d x_c / d t> for the covector c in WS_GC (public id ES_WS_TBAR)
     WS_COUNT
 };
-static_assert(WS_XCBAR == 27 && WS_CURV == 34 && WS_TBAR == 35 && WS_VBAR_C == 23,
-              "public buffer ids of include/endosurf_hip.h (ES_WS_XCBAR, ES_WS_CURV, ES_WS_TBAR, ES_WS_VBAR)");
+static_assert(WS_XC == ES_WS_XC && WS_V == ES_WS_V && WS_SDF == ES_WS_SDF && WS_FEAT == ES_WS_FEAT && WS_GC == ES_WS_GC && WS_GO == ES_WS_GO &&
+                  WS_RGB == ES_WS_RGB && WS_XCBAR == ES_WS_XCBAR && WS_CURV == ES_WS_CURV && WS_TBAR == ES_WS_TBAR && WS_VBAR_C == ES_WS_VBAR,
+              "public buffer ids of include/endosurf_hip.h");
 
 struct WsLayout {
     size_t off[WS_COUNT + 1];
@@ -108,6 +114,9 @@ inline WsLayout ws_layout(int M, int flags) {
     L.off[WS_COUNT] = o;
     return L;
 }
+
+// the points [0, M_color) that go through the colour network: m_color of them, or all M for m_color <= 0
+inline int color_points(int flags, int m_color, int M) { return (flags & PF_COLOR) ? (m_color > 0 ? m_color : M) : 0; }
 
 // a colour-less tail [m_color, M) behind a tile-aligned main part (the fused training batch): see point_fwd.hip
 inline bool aux_tail(int flags, int m_color, int M) {

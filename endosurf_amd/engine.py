@@ -506,7 +506,7 @@ class Engine(MeshMixin, EvalMixin):
                     hook(stage, dweff)
             return dweff
         check(self.lib.es_point_backward_det(C.byref(ctx.pts), ptr(packed), ptr(weff), ptr(ctx.ws), flags, ctx.m_color, ptr(d_sdf), ptr(d_go),
-                                             ptr(d_rgb) if color else None, ptr(dweff), ptr(self.wg_scratch()), self.st()), "es_point_backward")
+                                             ptr(d_rgb) if color else None, ptr(dweff), ptr(self.wg_scratch()), self.st()), "es_point_backward_det")
         return dweff
 
     def point_input_adjoint(self, ctx: PointCtx, weff, packed, d_sdf, d_go):
