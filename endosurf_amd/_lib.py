@@ -161,6 +161,8 @@ PROTOTYPES = {
     "es_surf_scratch_bytes": (C.c_int64, [C.c_longlong, C.c_longlong]),
     "es_surf_build": (_I, [_P, _P, C.c_longlong, C.c_longlong, _P, _P]),
     "es_surf_query": (_I, [_P, C.c_longlong, _P, _P, C.c_longlong, C.c_longlong, _P, _P, _P, _P, _P, _P]),
+    "es_cloud_self_nearest": (_I, [_P, C.c_longlong, _P, _P, _P, _P]),
+    "es_cloud_radius_count": (_I, [_P, C.c_longlong, C.c_longlong, _P, _P, _I, _P, _P]),
     "es_timing_enable": (_I, [_I]),
     "es_timing_drain": (_I, [_I, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "es_kernel_name": (C.c_char_p, [_I]),

@@ -465,30 +465,7 @@ __global__ __launch_bounds__(256) void k_nn_fill(const float* __restrict__ pts, 
     }
 }
 
-// (dx dx + dy dy) + dz dz with every product and sum rounded on its own: the library is built with -ffp-contract=fast, and a fused
-// multiply-add here would give other last bits than the numpy twin (and than a caller's own fp32 check)
-__device__ __forceinline__ float nn_dist2(float dx, float dy, float dz) {
-#pragma clang fp contract(off)
-    const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
-    const float s = xx + yy;
-    return s + zz;
-}
-
-// The correctly rounded square root of x >= 0, whatever the accuracy of the device's sqrtf (measured: it is not numpy's): the
-// neighbour s -+ 1 ulp replaces s when x lies beyond the midpoint between them, decided exactly -- a midpoint has 25 significant bits,
-// so its square is exact in fp64.  Two turns cover a start that is 2 ulp off.
-__device__ __forceinline__ float nn_sqrt_rn(float x) {
-    float s = sqrtf(x);
-    const double xd = (double)x;
-    for (int turn = 0; turn < 2 && s > 0.f; ++turn) {
-        const float lo = __int_as_float(__float_as_int(s) - 1), hi = __int_as_float(__float_as_int(s) + 1);
-        const double m1 = 0.5 * ((double)lo + (double)s), m2 = 0.5 * ((double)s + (double)hi);
-        if (xd < m1 * m1) s = lo;
-        else if (xd > m2 * m2) s = hi;
-        else break;
-    }
-    return s;
-}
+// (the squared distance nn_dist2 and the correctly rounded square root nn_sqrt_rn: nn_grid.h, shared with csrc/cloud.hip)
 
 // The records of cells [c0, c1] of one (x, y) column are contiguous (z fastest).  (d2, index) keeps the lexicographic minimum, so the
 // order of the records inside a cell does not show.

@@ -1,6 +1,7 @@
 // The uniform grid of the nearest-neighbour search (csrc/mesh.hip builds and queries it over points, csrc/surface.hip queries it over
-// triangle centroids): the header a build leaves in the scratch, the scratch layout, the cell function and the checks a kernel makes
-// before it trusts what the scratch holds.
+// triangle centroids, csrc/cloud.hip queries it over the points themselves): the header a build leaves in the scratch, the scratch
+// layout, the cell function, the checks a kernel makes before it trusts what the scratch holds, and the two pieces of arithmetic every
+// query shares (the uncontracted squared distance, the correctly rounded square root).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,6 +66,41 @@ __device__ __forceinline__ int nn_cell1(float x, float lo, float inv_h, int n) {
 // the header as a kernel may use it: dimensions that the buffers can hold, whatever the scratch held
 __device__ __forceinline__ bool nn_head_ok(const NnHeader& h, long long P) {
     return h.n[0] >= 1 && h.n[1] >= 1 && h.n[2] >= 1 && (long long)h.n[0] * h.n[1] <= P && (long long)h.n[0] * h.n[1] * h.n[2] <= P;
+}
+
+// (dx dx + dy dy) + dz dz with every product and sum rounded on its own: the library is built with -ffp-contract=fast, and a fused
+// multiply-add here would give other last bits than the numpy twin (and than a caller's own fp32 check)
+__device__ __forceinline__ float nn_dist2(float dx, float dy, float dz) {
+#pragma clang fp contract(off)
+    const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+    const float s = xx + yy;
+    return s + zz;
+}
+
+// nn_dist2 with every rounding where the source puts it.  The pragma above does not hold what it says: under -ffp-contract=fast the back
+// end still fuses one product into the sum (a v_fma_f32 in the ISA; the open point of DESIGN 7b).  An empty asm statement makes each
+// product a value the optimiser cannot look through, so it is rounded on its own and the sums are plain adds.  csrc/cloud.hip promises
+// its twins' bits and uses this one; k_nn_query keeps nn_dist2 and the one-ulp slack DESIGN 7b states.
+__device__ __forceinline__ float nn_dist2_exact(float dx, float dy, float dz) {
+    float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+    asm("" : "+v"(xx), "+v"(yy), "+v"(zz));
+    return (xx + yy) + zz;
+}
+
+// The correctly rounded square root of x >= 0, whatever the accuracy of the device's sqrtf (measured: it is not numpy's): the
+// neighbour s -+ 1 ulp replaces s when x lies beyond the midpoint between them, decided exactly -- a midpoint has 25 significant bits,
+// so its square is exact in fp64.  Two turns cover a start that is 2 ulp off.
+__device__ __forceinline__ float nn_sqrt_rn(float x) {
+    float s = sqrtf(x);
+    const double xd = (double)x;
+    for (int turn = 0; turn < 2 && s > 0.f; ++turn) {
+        const float lo = __int_as_float(__float_as_int(s) - 1), hi = __int_as_float(__float_as_int(s) + 1);
+        const double m1 = 0.5 * ((double)lo + (double)s), m2 = 0.5 * ((double)s + (double)hi);
+        if (xd < m1 * m1) s = lo;
+        else if (xd > m2 * m2) s = hi;
+        else break;
+    }
+    return s;
 }
 
 }  // namespace es

@@ -4,6 +4,7 @@ inverse-CDF pixel sampler and the per-iteration batch gather — as device-side 
 File decoding (imageio / cv2 / pickle info files) is out of scope: a ``FrameSet`` is built from arrays already in memory."""
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -89,6 +90,30 @@ class FrameSet:
         # at construction and no host round trip per batch afterwards
         self._tables = {}
         self._kept = {}
+
+    _OWN_ARGS = ("depth_masks", "near", "far", "normalize_time", "list_train", "device")
+
+    @classmethod
+    def from_raw(cls, colors, depths, intrinsics, poses, bounds, color_masks=None, **normalization_args):
+        """The ``FrameSet`` of a raw RGB-D sequence: metric depths [n,h,w] or [n,h,w,1], camera-to-world ``poses`` and ``bounds`` in
+        the depths' unit.  What the reference splits between data/*/preprocess.py and Dataset.__init__: ``scene_normalization`` of the
+        depths (masked by ``color_masks``), ``normalize_cameras``, depths and bounds divided by the scene radius.  The normalisation
+        runs on the frame set's ``device``; keywords that are not ``FrameSet``'s own (``_OWN_ARGS``) go to ``scene_normalization``.
+        ``scale_mat`` [4,4] fp32, ``depth_scale`` (float) and ``bbox_minmax`` [n,3,2] fp64 are kept as attributes, named as on the
+        reference's Dataset."""
+        own = {k: normalization_args.pop(k) for k in cls._OWN_ARGS if k in normalization_args}
+        dev = torch.device(own.get("device", "cuda"))
+        T = lambda a: None if a is None else torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a, dtype=torch.float32).to(dev)
+        d, k, c2w, cm = T(depths), T(intrinsics), T(poses), T(color_masks)
+        d = d[..., 0] if d.dim() == 4 else d
+        normalization_args.setdefault("masks", cm)
+        norm = scene_normalization(d, k, c2w, **normalization_args)
+        k_n, c2w_n = normalize_cameras(k, c2w, norm["scale_mat"])
+        scale = norm["depth_norm_scale"]
+        cm = cm[..., None] if cm is not None and cm.dim() == 3 else cm
+        fs = cls(colors, d[..., None] / scale, k_n, c2w_n, T(bounds) / scale, color_masks=cm, **own)
+        fs.scale_mat, fs.depth_scale, fs.bbox_minmax = norm["scale_mat"], scale, norm["bbox_minmax"]
+        return fs
 
     def _frame_tables(self, i: int):
         """(cdf [H*W] fp32, last kept pixel [] int64, colour-mask [H*W] bool) of frame ``i``; raises if its colour mask is empty
@@ -281,6 +306,155 @@ def cal_surface_error(points, vertices, triangles, depth_scale: float = 1.0, eng
     as_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
     dist = point_to_mesh(as_np(points), as_np(vertices), as_np(triangles))[0]
     return float(dist.astype(np.float64).mean()) * float(depth_scale) if dist.size else float("nan")
+
+
+# ---- scene normalisation (the reference's data/endonerf/preprocess.py:55-112 create_endonerf_info, without Open3D) -------
+def _as_f32(a, device=None):
+    """``a`` (numpy array or tensor) as an fp32 tensor, on ``device`` when one is given."""
+    t = torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a, dtype=torch.float32)
+    return t if device is None else t.to(device)
+
+
+def depth_percentile(values, q):
+    """np.percentile (linear) of the non-zero entries of ``values`` without an fp64 copy of them: with v the sorted non-zero fp32
+    values, M their number, p = q / 100 (M - 1) and k = floor(p): v[k] + (p - k)(v[k+1] - v[k]) in fp64.  ``q`` is one percentage
+    (-> float) or a sequence of them (-> tuple of floats, from one sort).  A device tensor is sorted on the device and the two
+    elements each q needs are read back (torch.quantile refuses inputs above 16 M elements); anything else is sorted by numpy."""
+    qs = [float(x) for x in (q if isinstance(q, (tuple, list, np.ndarray)) else [q])]
+    if any(not 0.0 <= x <= 100.0 for x in qs):
+        raise ValueError(f"percentiles must be in [0, 100] (got {q!r})")
+    if torch.is_tensor(values) and values.is_cuda:
+        x = values.detach().reshape(-1).float()
+        v = torch.sort(x[x != 0]).values
+    else:
+        x = (values.detach().cpu().numpy() if torch.is_tensor(values) else np.asarray(values)).astype(np.float32).reshape(-1)
+        v = np.sort(x[x != 0])
+    M = int(v.shape[0])
+    if M == 0:
+        raise ValueError("depth_percentile: there is no non-zero value")
+    ps = [x / 100.0 * (M - 1) for x in qs]
+    ks = [min(int(np.floor(p)), M - 1) for p in ps]
+    idx = [i for k in ks for i in (k, min(k + 1, M - 1))]
+    ends = v[torch.as_tensor(idx, device=v.device)].double().tolist() if torch.is_tensor(v) else v[idx].astype(np.float64).tolist()
+    out = tuple(ends[2 * i] + (p - k) * (ends[2 * i + 1] - ends[2 * i]) for i, (p, k) in enumerate(zip(ps, ks)))
+    return out if isinstance(q, (tuple, list, np.ndarray)) else out[0]
+
+
+def _compact(mask, *tensors):
+    """The rows of every tensor where ``mask`` is set (one count read back for all of them)."""
+    idx = torch.nonzero(mask).reshape(-1)
+    return [t[idx] for t in tensors]
+
+
+def _outlier_pass(pts, nb_points, radius_factor, engine):
+    """One radius-outlier pass over ``pts`` [P,3] as the reference runs it (preprocess.py:79-80): radius = ``radius_factor`` x the fp64
+    mean of the finite self-nearest distances, kept = ``radius_outlier_mask``.  (kept bool [P], radius 0-dim fp64), both on ``pts``'
+    device; on the GPU the radius never leaves it."""
+    if pts.is_cuda:
+        dist, _ = engine.self_nearest(pts)
+        fin = torch.isfinite(dist)
+        radius = float(radius_factor) * (torch.where(fin, dist, torch.zeros_like(dist)).double().sum() / fin.sum())
+        return engine.radius_outlier_mask(pts, nb_points, radius), radius
+    from .meshing import radius_outlier_mask, self_nearest
+    p = pts.numpy()
+    dist, _ = self_nearest(p)
+    fin = np.isfinite(dist)
+    radius = float(radius_factor) * (dist[fin].astype(np.float64).mean() if fin.any() else float("nan"))
+    return torch.from_numpy(radius_outlier_mask(p, nb_points, radius)), torch.tensor(radius, dtype=torch.float64)
+
+
+def scene_normalization(depths, intrinsics, poses, masks=None, percentiles=(3.0, 99.9), down_sample=1.0, u=None, nb_points=5,
+                        radius_factor=20.0, object_scale_in_sphere=0.6, pad=(-5.0, -5.0, 10.0), engine=None) -> Dict:
+    """The unit-sphere normalisation of a raw RGB-D sequence, as the reference's create_endonerf_info derives it through Open3D
+    (data/endonerf/preprocess.py:55-112): ``depths`` [n,H,W] (or [n,H,W,1]), ``intrinsics`` and camera-to-world ``poses`` [n,4,4],
+    ``masks`` [n,H,W(,1)] (0 = ignore the pixel).  Device tensors go through the ``Engine`` (one of their device is made when none is
+    given), anything else through the brute-force numpy twins of ``meshing`` -- O(P^2) per frame, so host arrays of real size want
+    ``down_sample`` well below 1, or the device.
+
+      1. depths are zeroed where ``masks == 0``; (close, inf) = ``depth_percentile`` of the non-zero depths at ``percentiles``; depths
+         above inf and non-zero depths below close are zeroed (compared in fp64);
+      2. per frame: ``depth_points(depth, K, pose, depth_trunc=inf)``; a pixel stays iff ``u[frame, y, x] < down_sample`` (``u``
+         [n,H,W] uniform draws, torch.rand when not given; skipped entirely at ``down_sample >= 1``) -- a Bernoulli draw per pixel,
+         where Open3D's random_down_sample shuffles and keeps an exact count; then one outlier pass: radius = ``radius_factor`` x the
+         fp64 mean self-nearest distance, kept iff more than ``nb_points`` rows within it (``meshing.radius_outlier_mask``); the
+         frame's box (lo_i, hi_i) is that of its kept points;
+      3. the kept points of all frames, concatenated, go through the same outlier pass once more;
+      4. centre = (lo + hi) / 2 of the merged box, radius = max |p - centre| / ``object_scale_in_sphere`` (fp64 on the fp32 points).
+
+    Returns ``scale_mat`` [4,4] fp32 (diag(radius, radius, radius, 1), the centre as translation), ``depth_norm_scale`` (= radius,
+    float), ``bbox_minmax`` [n,3,2] fp64 = stack([(lo_i - centre) / radius - pad / radius, (hi_i - centre) / radius + pad / radius], -1)
+    (``pad`` in the depths' unit), ``close_depth``, ``inf_depth`` (floats), ``counts`` (per frame: valid, sampled, kept; merged: the
+    kept total), ``points`` [kept total, 3] fp32, the merged cloud normalised into the sphere (frame by frame, pixel order inside a
+    frame) and ``kept_mask`` [n,H,W] bool, the pixels those points come from.  Tensors live on ``depths``' device.
+    A frame left without points raises ValueError.  Dropped rows are compacted, which costs the host one count per compaction."""
+    d = _as_f32(depths)
+    dev = d.device
+    d = d[..., 0] if d.dim() == 4 else d
+    k, c2w = _as_f32(intrinsics, dev), _as_f32(poses, dev)
+    n = int(d.shape[0])
+    if d.dim() != 3 or tuple(k.shape) != (n, 4, 4) or tuple(c2w.shape) != (n, 4, 4):
+        raise ValueError(f"scene_normalization takes depths [n,H,W], intrinsics and poses [n,4,4] (got {tuple(d.shape)}, {tuple(k.shape)}, {tuple(c2w.shape)})")
+    if masks is not None:
+        m = _as_f32(masks, dev)
+        d = torch.where((m[..., 0] if m.dim() == 4 else m) == 0, torch.zeros_like(d), d)
+    close, inf = depth_percentile(d, tuple(percentiles))
+    d64 = d.double()
+    d = torch.where((d64 > inf) | ((d64 < close) & (d64 != 0)), torch.zeros_like(d), d)
+    del d64
+    ratio = float(down_sample)
+    if ratio < 1.0:
+        u = torch.rand(d.shape, device=dev) if u is None else _as_f32(u, dev).reshape(d.shape)
+    if dev.type == "cuda":
+        engine = _engine_for(d, engine)
+    counts = {"valid": [], "sampled": [], "kept": [], "merged": 0}
+    clouds, pixels, boxes = [], [], []
+    hw = int(d.shape[1] * d.shape[2])
+    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+        for i in range(n):
+            pts = depth_points(d[i], k[i], c2w[i], depth_trunc=inf)
+            pix = torch.nonzero(((d[i] > 0) & (d[i] <= inf)).reshape(-1)).reshape(-1)          # depth_points' pixels, in its order
+            counts["valid"].append(int(pts.shape[0]))
+            if ratio < 1.0:
+                pts, pix = _compact(u[i].reshape(-1)[pix] < ratio, pts, pix)
+            counts["sampled"].append(int(pts.shape[0]))
+            pts, pix = _compact(_outlier_pass(pts, nb_points, radius_factor, engine)[0], pts, pix)
+            counts["kept"].append(int(pts.shape[0]))
+            if pts.shape[0] == 0:
+                raise ValueError(f"scene_normalization: frame {i} is left without points ({counts['valid'][-1]} valid pixels, "
+                                 f"{counts['sampled'][-1]} sampled)")
+            clouds.append(pts)
+            pixels.append(pix + i * hw)
+            boxes.append(torch.stack([pts.amin(0), pts.amax(0)]))
+        merged, pix = torch.cat(clouds), torch.cat(pixels)
+        merged, pix = _compact(_outlier_pass(merged, nb_points, radius_factor, engine)[0], merged, pix)
+    counts["merged"] = int(merged.shape[0])
+    if merged.shape[0] == 0:
+        raise ValueError("scene_normalization: the merged cloud is left without points")
+    kept_mask = torch.zeros(n * hw, dtype=torch.bool, device=dev)
+    kept_mask[pix] = True
+    p64 = merged.double()
+    centre = (p64.amin(0) + p64.amax(0)) / 2
+    radius = torch.linalg.norm(p64 - centre, dim=-1).max() / float(object_scale_in_sphere)
+    scale_mat = torch.diag(torch.cat([radius.expand(3), radius.new_ones(1)]))
+    scale_mat[:3, 3] = centre
+    box = torch.stack(boxes).double()          # [n, 2, 3]
+    pad_n = torch.as_tensor([float(x) for x in pad], dtype=torch.float64, device=dev) / radius
+    bbox_minmax = torch.stack([(box[:, 0] - centre) / radius - pad_n, (box[:, 1] - centre) / radius + pad_n], -1)
+    return {"scale_mat": scale_mat.float(), "depth_norm_scale": float(radius), "bbox_minmax": bbox_minmax, "close_depth": close, "inf_depth": inf,
+            "counts": counts, "points": ((p64 - centre) / radius).float(), "kept_mask": kept_mask.view(n, *d.shape[1:])}
+
+
+def normalize_cameras(intrinsics, poses, scale_mat):
+    """The cameras of the normalised scene: what the reference's Dataset.__init__ gets from decomposing ``world_mat @ scale_mat``
+    (src/dataset/dataset.py:51-58), in closed form.  ``scale_mat`` = [[r I, c], [0, 1]] is a similarity, so K [R^T | -R^T t] scale_mat
+    = r K [R^T | -R^T (t - c) / r]: the intrinsics and the rotation are unchanged, the camera centre becomes (t - c) / r (fp64, then
+    the poses' dtype).  ``intrinsics`` and camera-to-world ``poses`` [n,4,4] -> (intrinsics, poses), tensors on ``poses``' device."""
+    c2w = poses if torch.is_tensor(poses) else torch.as_tensor(np.asarray(poses))
+    k = (intrinsics if torch.is_tensor(intrinsics) else torch.as_tensor(np.asarray(intrinsics))).to(c2w.device)
+    s = (scale_mat if torch.is_tensor(scale_mat) else torch.as_tensor(np.asarray(scale_mat))).to(c2w.device).double()
+    out = c2w.clone()
+    out[..., :3, 3] = ((c2w[..., :3, 3].double() - s[:3, 3]) / s[0, 0]).to(c2w.dtype)
+    return k.clone(), out
 
 
 # ---- binary PLY files (the reference's demo writes its meshes through Open3D, trainer_endosurf.py:447-466; DESIGN.md 7e) ---------------

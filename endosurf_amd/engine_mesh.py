@@ -208,6 +208,53 @@ class MeshMixin:
         check(self.lib.es_nn_query(ptr(q), Q, P, ptr(scratch), ptr(dist), ptr(index), st), "es_nn_query")
         return dist, index
 
+    # ---- point-cloud clean-up queries (csrc/cloud.hip; contract: DESIGN.md 7g) ---------------------------------------------------
+    def _nn_grid(self, p32):
+        """The scratch ``es_nn_build`` leaves for the rows of ``p32``."""
+        scratch = self._scratch("es_nn_scratch_bytes", int(p32.shape[0]))
+        check(self.lib.es_nn_build(ptr(p32), int(p32.shape[0]), ptr(scratch), self.st()), "es_nn_build")
+        return scratch
+
+    def self_nearest(self, points: torch.Tensor):
+        """For each row of ``points`` [P, 3] its nearest other row: (dist [P] fp32, index [P] int32) by the rule of
+        ``meshing.self_nearest`` (the numpy twin and the specification): the smallest (fp32 squared distance, index) over the finite
+        rows j != i, so a duplicate of the point gives 0; inf / -1 for a non-finite row and for a row without another finite row.
+        Bit-identical from call to call; no read-back."""
+        p = self._rows3_arg(points, "self_nearest", "[N, 3] points")
+        P = int(p.shape[0])
+        dist, index = self.empty(P), self.empty(P, dtype=torch.int32)
+        check(self.lib.es_cloud_self_nearest(ptr(p), P, ptr(self._nn_grid(p)), ptr(dist), ptr(index), self.st()), "es_cloud_self_nearest")
+        return dist, index
+
+    def radius_count(self, query: torch.Tensor, points: torch.Tensor, radius=None, cap: int = 0, radius_sq=None):
+        """count [Q] int32 = the number of finite rows of ``points`` [P, 3] whose fp32 squared distance to the ``query`` row is <= r2, by
+        the rule of ``meshing.radius_count`` (the numpy twin and the specification).  ``radius`` is a Python float or a 0-dim tensor on
+        this device (no read-back either way) and is squared in fp32; ``radius_sq`` gives r2 itself instead.  A query that is a row of
+        ``points`` counts itself; a non-finite query row, or r2 NaN or negative, gives 0; ``cap`` > 0 gives min(count, cap) and stops
+        reading there.  Bit-identical from call to call."""
+        q, p = self._rows3_arg(query, "radius_count", "[N, 3] query"), self._rows3_arg(points, "radius_count", "[N, 3] points")
+        if (radius is None) == (radius_sq is None):
+            raise EndoSurfHipError("radius_count takes either radius or radius_sq")
+        cap = int(cap)
+        if cap < 0:
+            raise EndoSurfHipError(f"radius_count: cap must be >= 0 (got {cap})")
+        r = torch.as_tensor(radius if radius_sq is None else radius_sq).to(self.device).float().reshape(-1)
+        if r.numel() != 1:
+            raise EndoSurfHipError(f"radius_count takes one radius (got {r.numel()} values)")
+        r2 = (r * r if radius_sq is None else r).contiguous()
+        Q, P = int(q.shape[0]), int(p.shape[0])
+        count = self.empty(Q, dtype=torch.int32)
+        check(self.lib.es_cloud_radius_count(ptr(q), Q, P, ptr(self._nn_grid(p)), ptr(r2), cap, ptr(count), self.st()), "es_cloud_radius_count")
+        return count
+
+    def radius_outlier_mask(self, points: torch.Tensor, nb_points: int, radius):
+        """bool [P]: the rows of ``points`` with more than ``nb_points`` rows within ``radius``, themselves included
+        (``meshing.radius_outlier_mask`` is the numpy twin and the specification); False for a non-finite row.  No read-back."""
+        nb = int(nb_points)
+        if nb < 0:
+            raise EndoSurfHipError(f"radius_outlier_mask: nb_points must be >= 0 (got {nb_points!r})")
+        return self.radius_count(points, points, radius, cap=nb + 1) > nb
+
     # ---- point-to-surface distance (csrc/surface.hip; contract: DESIGN.md 7f) ------------------------------------------------
     def point_to_mesh(self, points: torch.Tensor, vertices: torch.Tensor, triangles: torch.Tensor, return_work: bool = False):
         """Exact distance from each row of ``points`` [Q, 3] to the triangle mesh ``vertices`` [V, 3] / ``triangles`` [T, 3] (int32 or

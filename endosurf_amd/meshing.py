@@ -299,6 +299,83 @@ def nearest(query, points, chunk=1 << 22):
     return np.sqrt(best), arg.astype(np.int32)
 
 
+# ---- point-cloud clean-up queries (host twins of csrc/cloud.hip; contract: DESIGN.md 7g) -----------------------------------------------
+def _cloud_rows(a):
+    a = np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, 3))
+    if len(a) >= 1 << 31:
+        raise ValueError("point / query counts must be below 2^31")
+    return a
+
+
+def _d2_rows(q, pf):
+    """fp32 (dx dx + dy dy) + dz dz of every row of ``q`` against every row of ``pf``: [len(q), len(pf)]."""
+    d = q[:, None, :] - pf[None, :, :]
+    d *= d
+    return (d[..., 0] + d[..., 1]) + d[..., 2]
+
+
+def self_nearest(points, chunk=1 << 22):
+    """For each row of ``points`` its nearest OTHER row (numpy twin of ``Engine.self_nearest``, chunked brute force; what Open3D's
+    compute_nearest_neighbor_distance measures): for a finite row i the lexicographic minimum of (d2, j) over the finite rows j != i, d2
+    the fp32 squared distance of ``nearest``; dist = its square root.  A duplicate of the point gives 0.  A non-finite row, a row
+    without another finite row and a row whose every d2 overflows get inf and -1.  Returns (dist [P] float32, index [P] int32)."""
+    p = _cloud_rows(points)
+    best = np.full(len(p), np.inf, np.float32)
+    arg = np.full(len(p), -1, np.int64)
+    ids = np.nonzero(np.isfinite(p).all(axis=1))[0]
+    pf = p[ids]
+    rows = max(1, int(chunk) // max(len(pf), 1))
+    with np.errstate(over="ignore", invalid="ignore"):
+        for q0 in range(0, len(pf) if len(pf) > 1 else 0, rows):
+            d2 = _d2_rows(pf[q0:q0 + rows], pf)
+            m = np.arange(len(d2))
+            d2[m, q0 + m] = np.inf                   # the row itself
+            d2[~np.isfinite(d2)] = np.inf          # (an overflow)
+            k = np.argmin(d2, axis=1)               # the first minimum: pf is in index order
+            v = d2[m, k]
+            hit = np.isfinite(v)
+            best[ids[q0:q0 + rows]] = np.where(hit, v, np.inf)
+            arg[ids[q0:q0 + rows]] = np.where(hit, ids[k], -1)
+    return np.sqrt(best), arg.astype(np.int32)
+
+
+def radius_count(query, points, radius=None, cap=0, radius_sq=None, chunk=1 << 22):
+    """How many rows of ``points`` lie within a radius of each ``query`` row (numpy twin of ``Engine.radius_count``, chunked brute
+    force): count[q] = the number of finite rows p with fp32 d2(q, p) <= r2, d2 the squared distance of ``nearest`` and
+    r2 = float32(radius) x float32(radius) in fp32 (only the square of ``radius`` matters), or ``radius_sq`` itself.  A query that is a
+    row of ``points`` counts itself.  A non-finite query row gives 0; r2 NaN or negative gives 0 everywhere; r2 = inf gives the number of
+    finite rows.  ``cap`` > 0 gives min(count, cap).  Returns count [Q] int32."""
+    q, p = _cloud_rows(query), _cloud_rows(points)
+    if (radius is None) == (radius_sq is None):
+        raise ValueError("radius_count takes either radius or radius_sq")
+    if int(cap) < 0:
+        raise ValueError(f"cap must be >= 0 (got {cap!r})")
+    with np.errstate(over="ignore", invalid="ignore"):
+        r2 = np.float32(radius_sq) if radius is None else np.float32(radius) * np.float32(radius)
+        count = np.zeros(len(q), np.int64)
+        if not r2 >= 0:
+            return count.astype(np.int32)
+        pf = p[np.isfinite(p).all(axis=1)]
+        qids = np.nonzero(np.isfinite(q).all(axis=1))[0]
+        rows = max(1, int(chunk) // max(len(pf), 1))
+        for q0 in range(0, len(qids) if len(pf) else 0, rows):
+            sel = qids[q0:q0 + rows]
+            count[sel] = (_d2_rows(q[sel], pf) <= r2).sum(axis=1)          # (an overflowed d2 is inf: within r2 = inf only)
+    return (np.minimum(count, int(cap)) if int(cap) > 0 else count).astype(np.int32)
+
+
+def radius_outlier_mask(points, nb_points, radius):
+    """bool [P]: the rows of ``points`` that a radius-outlier filter keeps (numpy twin of ``Engine.radius_outlier_mask``): a row is
+    kept iff more than ``nb_points`` rows lie within ``radius`` of it, itself included, i.e.
+    ``radius_count(points, points, radius, cap=nb_points + 1) > nb_points``; a non-finite row is never kept.  This is Open3D's
+    ``remove_radius_outlier(nb_points, radius)`` as remembered (its search returns the point itself, and it keeps a point with more
+    than ``nb_points`` results); the rule is NOT pinned against Open3D, which this project does not have at hand."""
+    nb = int(nb_points)
+    if nb < 0:
+        raise ValueError(f"nb_points must be >= 0 (got {nb_points!r})")
+    return radius_count(points, points, radius, cap=nb + 1) > nb
+
+
 # ---- point-to-surface distance (host twin of csrc/surface.hip; contract: DESIGN.md 7f) ------------------------------------------------
 def _dot3(a, b):          # vectors are tuples of three component arrays: no [..., 3] temporaries
     return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
