@@ -118,6 +118,9 @@ PROTOTYPES = {
     "es_iso_scratch_bytes": (C.c_int64, [_I, _I, _I]),
     "es_iso_count": (_I, [_P, _I, _I, _I, C.c_double, _P, _P, _P]),
     "es_iso_emit": (_I, [_P, _I, _I, _I, C.c_double, _P, C.c_longlong, C.c_longlong, _P, _P, _P, _P]),
+    "es_cubes_scratch_bytes": (C.c_int64, [_I, _I, _I]),
+    "es_cubes_count": (_I, [_P, _I, _I, _I, C.c_double, _P, _P, _P]),
+    "es_cubes_emit": (_I, [_P, _I, _I, _I, C.c_double, _P, C.c_longlong, C.c_longlong, _P, _P, _P, _P]),
     "es_band_scratch_bytes": (C.c_int64, [_I, _I, _I, _I]),
     "es_band_lattice_points": (_I, [_P, _P, _P, _I, _I, _I, _I, C.c_longlong, C.c_longlong, _P, _P]),
     "es_band_seed": (_I, [_P, _I, _I, _I, _I, C.c_double, C.c_double, _P, _P, _P]),

@@ -43,22 +43,31 @@ class MeshMixin:
             raise EndoSurfHipError(f"{what} takes [V, 1..{RAST_MAX_ATTRS}] attributes on {self.device} (got {tuple(attributes.shape)})")
         return f32(attributes), int(attributes.shape[1])
 
-    # ---- iso-surface extraction (csrc/iso.hip) -------------------------------------------------------
-    def iso_surface(self, field: torch.Tensor, threshold: float = 0.0):
+    # ---- iso-surface extraction (csrc/iso.hip, csrc/cubes.hip) ----------------------------------------
+    ISO_METHODS = {"tetrahedra": "es_iso", "cubes": "es_cubes"}          # method -> the prefix of its three library calls
+
+    def iso_surface(self, field: torch.Tensor, threshold: float = 0.0, method: str = "tetrahedra"):
         """The level set ``field == threshold`` of a device field [nx, ny, nz] as a welded, oriented triangle mesh, triangulated like
         ``meshing.marching_tetrahedra``: (verts [V,3] fp32 in index coordinates, tris [T,3] int32, edge_ends [V,2] int32 = linear grid
-        ids of each vertex's inside and outside end), all on the device.  The two counts are the only thing read back to the host."""
+        ids of each vertex's inside and outside end), all on the device.  The two counts are the only thing read back to the host.
+        ``method="cubes"`` triangulates like ``meshing.marching_cubes`` instead (csrc/cubes.hip: this project's cube table): the
+        vertices on the grid's axis edges only, bit for bit those the default method puts there, about a third of the vertices and
+        triangles."""
+        if method not in self.ISO_METHODS:
+            raise EndoSurfHipError(f"iso_surface: method must be one of {sorted(self.ISO_METHODS)} (got {method!r})")
         if field.dim() != 3 or field.device != self.device:
             raise EndoSurfHipError(f"iso_surface takes a [nx, ny, nz] field on {self.device} (got {tuple(field.shape)} on {field.device})")
+        fn = {k: f"{self.ISO_METHODS[method]}_{k}" for k in ("scratch_bytes", "count", "emit")}
         u = f32(field)
         nx, ny, nz = (int(s) for s in u.shape)
-        scratch, totals = self._scratch("es_iso_scratch_bytes", nx, ny, nz), self.empty(2, dtype=torch.int64)
-        check(self.lib.es_iso_count(ptr(u), nx, ny, nz, float(threshold), ptr(scratch), ptr(totals), self.st()), "es_iso_count")
+        scratch, totals = self._scratch(fn["scratch_bytes"], nx, ny, nz), self.empty(2, dtype=torch.int64)
+        check(getattr(self.lib, fn["count"])(ptr(u), nx, ny, nz, float(threshold), ptr(scratch), ptr(totals), self.st()), fn["count"])
         V, T = (int(v) for v in totals.tolist())
         if max(V, T) >= 1 << 31:
             raise EndoSurfHipError(f"iso_surface: {V} vertices / {T} triangles do not fit int32 indices")
         verts, ends, tris = self.empty(V, 3), self.empty(V, 2, dtype=torch.int32), self.empty(T, 3, dtype=torch.int32)
-        check(self.lib.es_iso_emit(ptr(u), nx, ny, nz, float(threshold), ptr(scratch), V, T, ptr(verts), ptr(ends), ptr(tris), self.st()), "es_iso_emit")
+        check(getattr(self.lib, fn["emit"])(ptr(u), nx, ny, nz, float(threshold), ptr(scratch), V, T, ptr(verts), ptr(ends), ptr(tris), self.st()),
+              fn["emit"])
         return verts, tris, ends
 
     # ---- narrow-band field (csrc/band.hip) ---------------------------------------------------------------
@@ -121,14 +130,17 @@ class MeshMixin:
         return field.view(nx, ny, nz), stats, block_round.clone()
 
     def iso_surface_band(self, sample, axes, threshold: float = 0.0, block: int = 8, lipschitz: float = 1.0, max_fraction: float = 0.5,
-                         net_chunk: int = 1 << 22):
+                         net_chunk: int = 1 << 22, method: str = "tetrahedra"):
         """``iso_surface`` of the field ``sample`` takes on the lattice ``axes``, sampled near the level set only (``band_field``):
         (verts, tris, edge_ends, stats).  The mesh holds, complete and bit-identical, every vertex-connected component of the dense
         lattice's mesh that crosses a seed block: all of it when |grad u| <= ``lipschitz`` holds in the blocks that were culled.  With
         a smaller ``lipschitz`` (0 = sign changes of the block corners only) a closed component smaller than a block that no block
-        corner sees can be lost."""
+        corner sees can be lost.  ``method`` is ``iso_surface``'s: the band field guarantees the inside flags of every grid point a
+        crossing tetrahedron edge touches, and the cube triangulation's axis edges are among those."""
+        if method not in self.ISO_METHODS:
+            raise EndoSurfHipError(f"iso_surface_band: method must be one of {sorted(self.ISO_METHODS)} (got {method!r})")
         field, stats, _ = self.band_field(sample, axes, threshold, block, lipschitz, max_fraction, net_chunk)
-        verts, tris, ends = self.iso_surface(field, threshold)
+        verts, tris, ends = self.iso_surface(field, threshold, method)
         return verts, tris, ends, stats
 
     # ---- connected components, largest-component filter, nearest neighbour (csrc/mesh.hip) ----------------------------

@@ -4,7 +4,8 @@ The reference delegates to PyMCubes (``mcubes.marching_cubes``, src/renderer/uti
 un-vendored third-party dependency; parity unpinned).  When ``mcubes`` is importable it is used, otherwise this module's
 marching-tetrahedra extractor (vectorised numpy, host side: it runs once per frame on a field that was sampled on the GPU and
 copied back in a single transfer) produces a watertight mesh of the same level set in the same index-space coordinates.
-The triangulation differs from PyMCubes' (6 tetrahedra per cell instead of the cube table)."""
+The triangulation differs from PyMCubes' (6 tetrahedra per cell instead of the cube table).  ``marching_cubes`` is a second extractor with
+a cube table of this project's own (not PyMCubes'): the numpy twin of the device path's ``method="cubes"``, never chosen by default."""
 from __future__ import annotations
 
 import numpy as np
@@ -82,6 +83,130 @@ def marching_tetrahedra(u: np.ndarray, threshold: float = 0.0):
     tris[flip] = tris[flip][:, [0, 2, 1]]
     keep = (tris[:, 0] != tris[:, 1]) & (tris[:, 1] != tris[:, 2]) & (tris[:, 0] != tris[:, 2])
     return verts, tris[keep]
+
+
+# ---- cube triangulation (numpy twin of csrc/cubes.hip; the rule is this project's own: DESIGN.md 7a "Cube triangulation") ---------------
+# the 12 cube edges as (owner corner, direction code 4 dx + 2 dy + dz of the axis): edge id = position in this list
+CUBE_EDGES = tuple((oc, d) for oc in range(8) for d in (1, 2, 4) if not oc & d)
+# the 6 cube faces: their 4 corners in cyclic order
+CUBE_FACES = tuple(tuple(side * a + o for o in (0, b, b + c, c)) for a, b, c in ((4, 2, 1), (2, 4, 1), (1, 4, 2)) for side in (0, 1))
+_EDGE_ID = {frozenset((oc, oc | d)): i for i, (oc, d) in enumerate(CUBE_EDGES)}
+_cubes_cache = {}
+
+
+def cube_edges_share_face(e1, e2):
+    """Do the cube edges with ids ``e1`` and ``e2`` lie on one cube face?"""
+    ends = {CUBE_EDGES[e1][0], sum(CUBE_EDGES[e1]), CUBE_EDGES[e2][0], sum(CUBE_EDGES[e2])}
+    return any(ends <= set(face) for face in CUBE_FACES)
+
+
+def cube_case_loops(case):
+    """The closed loops of crossing edges (edge ids) of one of the 256 cell cases (bit c = corner c inside), each starting at its
+    smallest edge id and oriented so that its normal points from the inside corners to the outside ones.
+
+    On every face the crossing edges are joined by segments: two crossing edges by one segment; four (diagonal corners inside) by
+    cutting off each inside corner, i.e. joining the two edges that meet at it.  The rule reads the face's four flags only, so the two
+    cells that share a face draw the same segments."""
+    ins = [(case >> c) & 1 for c in range(8)]
+    nbr = {}
+    for face in CUBE_FACES:
+        fe = [_EDGE_ID[frozenset((face[i], face[(i + 1) % 4]))] for i in range(4)]          # edge i joins corners i and i + 1
+        cr = [i for i in range(4) if ins[face[i]] != ins[face[(i + 1) % 4]]]
+        segs = [(fe[cr[0]], fe[cr[1]])] if len(cr) == 2 else [(fe[(i - 1) % 4], fe[i]) for i in range(4) if ins[face[i]]] if len(cr) == 4 else []
+        for a, b in segs:
+            nbr.setdefault(a, []).append(b)
+            nbr.setdefault(b, []).append(a)
+    assert all(len(v) == 2 and v[0] != v[1] for v in nbr.values()), case
+    corner = _CORNER.astype(np.float64)
+    loops, todo = [], set(nbr)
+    while todo:
+        start = min(todo)
+        loop, prev, cur = [start], start, nbr[start][0]
+        while cur != start:
+            loop.append(cur)
+            prev, cur = cur, nbr[cur][0] if nbr[cur][0] != prev else nbr[cur][1]
+        todo -= set(loop)
+        assert 3 <= len(loop) <= 7, (case, loop)
+        mid = np.array([0.5 * (corner[CUBE_EDGES[e][0]] + corner[sum(CUBE_EDGES[e])]) for e in loop])
+        newell = np.cross(mid, np.roll(mid, -1, axis=0)).sum(axis=0)
+        out_minus_in = sum((corner[sum(CUBE_EDGES[e])] - corner[CUBE_EDGES[e][0]]) * (1.0 if ins[CUBE_EDGES[e][0]] else -1.0) for e in loop)
+        s = float(newell @ out_minus_in)
+        assert s != 0.0, (case, loop)
+        loops.append(loop if s > 0 else [loop[0]] + loop[:0:-1])
+    return loops
+
+
+def cube_fan(loop):
+    """The fan that triangulates ``loop``: its apex is the first loop position whose fan has no diagonal joining two edges of one
+    cube face (such a diagonal coincides with a segment the neighbouring cell may draw: a mesh edge used four times)."""
+    n = len(loop)
+    for k in range(n):
+        r = loop[k:] + loop[:k]
+        if not any(cube_edges_share_face(r[0], r[i]) for i in range(2, n - 1)):
+            return [(r[0], r[i], r[i + 1]) for i in range(1, n - 1)]
+    raise AssertionError(f"no fan without a face diagonal for loop {loop}")
+
+
+def cubes_table():
+    """table [256, 5, 3] int64: corner j of triangle k of a cell case as a cube edge id (index into CUBE_EDGES), -1 where there is
+    none.  Loops in ascending order of their first edge, triangles in fan order, normals from inside to outside."""
+    if "table" not in _cubes_cache:
+        table = np.full((256, 5, 3), -1, np.int64)
+        for case in range(256):
+            tris = [t for loop in cube_case_loops(case) for t in cube_fan(loop)]
+            assert len(tris) <= 5, case
+            table[case, :len(tris)] = np.array(tris, np.int64).reshape(-1, 3)
+        _cubes_cache["table"] = table
+    return _cubes_cache["table"]
+
+
+def marching_cubes(u: np.ndarray, threshold: float = 0.0, return_ends: bool = False):
+    """(vertices [V,3] float64 in index coordinates, triangles [T,3] int64[, edge_ends [V,2] int64]) of the level set u == threshold
+    by this project's cube triangulation (``cubes_table``): numpy twin of ``Engine.iso_surface(method="cubes")`` and its specification.
+
+    Conventions are ``marching_tetrahedra``'s: 'inside' = u < threshold (NaN and u == threshold are outside), a vertex sits on an axis
+    edge of the grid and is named by (inside end, outside end) as linear grid ids, its position is the same fp64 expression (a cube
+    vertex equals the tetrahedra vertex on that edge bit for bit), normals point to increasing u -- by the table, not by a cross
+    product.  Vertices are ordered by (linear id of the smaller end, direction code 4 dx + 2 dy + dz: z, then y, then x), triangles
+    by (cell linear id, position in the table row).  Degenerate positions (a vertex on a grid point) are kept."""
+    u = np.asarray(u, np.float64)
+    empty = (np.zeros((0, 3), np.float64), np.zeros((0, 3), np.int64)) + ((np.zeros((0, 2), np.int64),) if return_ends else ())
+    if u.ndim != 3 or min(u.shape) < 2:
+        return empty
+    nx, ny, nz = u.shape
+    inside = u < threshold
+    stride = np.array([1, nz, ny * nz], np.int64)                          # of the axes in slot order: z, y, x
+    cross = np.zeros((nx, ny, nz, 3), bool)                                # slot (p, k): the edge from p along axis k crosses the level
+    cross[:, :, :-1, 0] = inside[:, :, :-1] != inside[:, :, 1:]
+    cross[:, :-1, :, 1] = inside[:, :-1, :] != inside[:, 1:, :]
+    cross[:-1, :, :, 2] = inside[:-1, :, :] != inside[1:, :, :]
+    flat = cross.reshape(-1)
+    slots = np.nonzero(flat)[0]
+    if slots.size == 0:
+        return empty
+    vid = np.cumsum(flat) - 1                                              # vertex id of a slot
+    p, k = slots // 3, slots % 3
+    q = p + stride[k]
+    pin = inside.reshape(-1)[p]
+    ea, eb = np.where(pin, p, q), np.where(pin, q, p)
+    ua, ub = u.reshape(-1)[ea], u.reshape(-1)[eb]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        w = (threshold - ua) / (ub - ua)
+        pa = np.stack(np.unravel_index(ea, u.shape), -1).astype(np.float64)
+        pb = np.stack(np.unravel_index(eb, u.shape), -1).astype(np.float64)
+        verts = pa + w[:, None] * (pb - pa)
+    # triangles: the table row of every cell, its edge ids turned into slots of the cell's corner points
+    case = np.zeros((nx - 1, ny - 1, nz - 1), np.int64)
+    for c, (dx, dy, dz) in enumerate(_CORNER):
+        case |= inside[dx:nx - 1 + dx, dy:ny - 1 + dy, dz:nz - 1 + dz].astype(np.int64) << c
+    ci, cj, ck = np.nonzero((case > 0) & (case < 255))
+    rows = cubes_table()[case[ci, cj, ck]]                                 # [C,5,3] edge ids
+    owner = np.array([(oc >> 2) * stride[2] + ((oc >> 1) & 1) * stride[1] + (oc & 1) for oc, _ in CUBE_EDGES], np.int64)
+    rank = np.array([{1: 0, 2: 1, 4: 2}[d] for _, d in CUBE_EDGES], np.int64)
+    cell = ((ci * ny + cj) * nz + ck)[:, None, None]
+    e = np.maximum(rows, 0)
+    tris = vid[(cell + owner[e]) * 3 + rank[e]][rows[..., 0] >= 0].astype(np.int64).reshape(-1, 3)
+    return (verts, tris, np.stack([ea, eb], -1).astype(np.int64)) if return_ends else (verts, tris)
 
 
 def iso_surface(u: np.ndarray, threshold: float = 0.0):

@@ -44,17 +44,20 @@ class RendererMeshMixin:
         launches of ``net_chunk`` points and returned with ONE device-to-host copy as numpy [R,R,R] (x-major like the reference)."""
         return self._field_on_device(bound_min, bound_max, resolution, t, net_chunk).cpu().numpy()
 
-    def _mesh_on_device(self, t, bound_min, bound_max, resolution, threshold, net_chunk, band=None, counts=None):
+    def _mesh_on_device(self, t, bound_min, bound_max, resolution, threshold, net_chunk, band=None, counts=None, method="tetrahedra"):
         """(vertices [V,3] in world coordinates, triangles [T,3] int32) as device tensors: field, iso-surface and the index -> world map
         all on the GPU (the field never leaves it; the host reads the two counts).  ``band``: True or a dict of block / lipschitz /
-        max_fraction samples near the surface only, and ``Engine.band_field``'s counts go to ``counts["stats"]`` if ``counts`` is a dict."""
+        max_fraction samples near the surface only, and ``Engine.band_field``'s counts go to ``counts["stats"]`` if ``counts`` is a dict.
+        ``method``: ``Engine.iso_surface``'s triangulation, "tetrahedra" or "cubes"."""
+        if method not in self.engine.ISO_METHODS:          # (before the field is sampled)
+            raise ValueError(f"method must be one of {sorted(self.engine.ISO_METHODS)} (got {method!r})")
         if band is None or band is False:
             u = self._field_on_device(bound_min, bound_max, resolution, t, net_chunk)
         else:
             u, stats = self._band_field_on_device(bound_min, bound_max, resolution, t, threshold, net_chunk, {} if band is True else dict(band))
             if counts is not None:
                 counts["stats"] = stats
-        verts, tris, _ = self.engine.iso_surface(u, threshold)
+        verts, tris, _ = self.engine.iso_surface(u, threshold, method)
         return _Lattice(bound_min, bound_max, resolution, self.device).to_world(verts), tris
 
     @staticmethod
@@ -93,7 +96,7 @@ class RendererMeshMixin:
 
     @_on_device
     def extract_observation_geometry(self, t, bound_min, bound_max, resolution, threshold=0.0, net_chunk=1 << 22, cpu=True, on_device=False,
-                                     band=None, components=None):
+                                     band=None, components=None, method="tetrahedra"):
         """(vertices, triangles) of the observed-space surface at time t (reference endosurf.py:490-500 + extract_geometry,
         utils.py:128-136).  Field sampling runs on the GPU.  By default the field is copied to the host and the iso-surface extractor
         is PyMCubes when installed (as in the reference), otherwise endosurf_amd.meshing.marching_tetrahedra (different triangulation
@@ -102,14 +105,18 @@ class RendererMeshMixin:
         ``band=True`` or ``band=dict(block=8, lipschitz=1.0, max_fraction=0.5)`` queries the SDF near the surface only (see
         ``extract_observation_mesh``); the default ``None`` samples every grid point.  With ``on_device``, ``components=0.9`` (or True,
         or dict(keep_ratio=0.9, compact=True)) keeps the largest connected components only (``Engine.keep_components``; see
-        ``extract_observation_mesh``); the default ``None`` keeps every triangle."""
+        ``extract_observation_mesh``); the default ``None`` keeps every triangle.  With ``on_device``, ``method="cubes"`` triangulates
+        with this project's cube table (``meshing.marching_cubes``, csrc/cubes.hip: a third of the vertices and triangles; not
+        PyMCubes' table) instead of the default "tetrahedra"."""
         comp = self._components_arg(components)
+        if method != "tetrahedra" and not on_device:
+            raise ValueError("method needs on_device=True (the host path is meshing.iso_surface: PyMCubes, else marching tetrahedra)")
         if band is not None and band is not False and not on_device:
             raise ValueError("band needs on_device=True (the narrow-band field is assembled on the GPU)")
         if comp is not None and not on_device:
             raise ValueError("components needs on_device=True (the component filter runs on the GPU)")
         if on_device:
-            vertices, triangles = self._mesh_on_device(t, bound_min, bound_max, resolution, threshold, net_chunk, band)
+            vertices, triangles = self._mesh_on_device(t, bound_min, bound_max, resolution, threshold, net_chunk, band, method=method)
             if comp is not None:
                 vertices, triangles, _, _ = self.engine.keep_components(vertices, triangles, **comp)
             return (vertices.cpu().numpy(), triangles.cpu().numpy()) if cpu else (vertices, triangles)
@@ -122,7 +129,7 @@ class RendererMeshMixin:
 
     @_on_device
     def extract_observation_mesh(self, t, bound_min, bound_max, resolution, threshold=0.0, net_chunk=1 << 22, view_point=None, refine_steps=0,
-                                 band=None, components=None, clean=False, simplify=None):
+                                 band=None, components=None, clean=False, simplify=None, method="tetrahedra"):
         """The observed-space surface at time t as a coloured mesh, device tensors only (what the reference's demo assembles from
         extract_observation_geometry + renderonpts, trainer_endosurf.py:403-460): ``vertices`` [V,3] world coordinates, ``triangles``
         [T,3] int32, ``normals`` [V,3] the analytic observed-space SDF gradient at the vertices normalised as renderonpts does, ``sdf``
@@ -157,10 +164,17 @@ class RendererMeshMixin:
         the extraction lattice, counted from ``bound_min``) then merges the vertices of each cell into their mean
         (``Engine.cluster_vertices``, which cleans behind itself) before refinement, normals and colours, which are therefore evaluated
         at the clustered vertices, not averaged; it adds ``simplify`` (cells, largest_cell, degenerate, duplicates, kept_triangles).
-        Both are off by default, and the mesh is then bit for bit what it was without these keywords."""
+        Both are off by default, and the mesh is then bit for bit what it was without these keywords.
+
+        ``method="cubes"`` extracts with this project's cube triangulation (``Engine.iso_surface(method="cubes")``,
+        ``meshing.marching_cubes``) instead of the default "tetrahedra": the vertices on the lattice's axis edges only, about a third
+        of the vertices and triangles, so every later step -- filter, clean-up, clustering, refinement, normals, colours, export --
+        handles a third of the elements.  The result then carries ``method``.  Band and dense agree as they do by default."""
         comp = self._components_arg(components)
         counts = {}          # the dicts of counts the result carries, by its key
-        vertices, triangles = self._mesh_on_device(t, bound_min, bound_max, resolution, threshold, net_chunk, band, counts)
+        vertices, triangles = self._mesh_on_device(t, bound_min, bound_max, resolution, threshold, net_chunk, band, counts, method)
+        if method != "tetrahedra":
+            counts["method"] = method
         if comp is not None:
             vertices, triangles, _, counts["components"] = self.engine.keep_components(vertices, triangles, **comp)
         if clean:
@@ -217,13 +231,14 @@ class RendererMeshMixin:
 
     @_on_device
     def export_observation_mesh(self, prefix, t, bound_min, bound_max, resolution, threshold=0.0, view_point=None, components=0.9, simplify=None,
-                                **extract_kwargs):
+                                method="tetrahedra", **extract_kwargs):
         """The three mesh files of the reference's demo for one frame (trainer_endosurf.py:435-466), without Open3D:
         ``prefix + "_geometry.ply"`` (vertices and triangles), ``prefix + "_color.ply"`` (plus the ``renderonpts`` colours clipped to
         [0, 1]; white without a ``view_point``, as there is no direction to render from) and ``prefix + "_normal.ply"`` (plus the
         paint (-n 0.5 + 0.5).clip(0, 1) of the normals ``Engine.vertex_normals`` computes from the triangles, the demo's
         compute_vertex_normals).  The mesh is that of ``extract_observation_mesh`` with the component filter (``components``, 0.9 as in
-        the demo; None for none), always cleaned of degenerate and duplicate triangles, and clustered when ``simplify`` is given;
+        the demo; None for none), always cleaned of degenerate and duplicate triangles, clustered when ``simplify`` is given, and
+        triangulated by ``method`` ("tetrahedra", or "cubes" for files a third of the size);
         ``extract_kwargs`` (net_chunk, refine_steps, band) are passed on.  Files are ``data.write_ply``'s: binary little endian, fp32
         coordinates, the body packed on the device, one copy to the host per file.  Returns the mesh dict with ``vertex_normals``
         [V, 3] and ``paths`` (geometry, color, normal)."""
@@ -231,7 +246,7 @@ class RendererMeshMixin:
         if unknown:
             raise TypeError(f"export_observation_mesh passes net_chunk, refine_steps and band on (got {sorted(unknown)})")
         mesh = self.extract_observation_mesh(t, bound_min, bound_max, resolution, threshold=threshold, view_point=view_point, components=components,
-                                             clean=True, simplify=simplify, **extract_kwargs)
+                                             clean=True, simplify=simplify, method=method, **extract_kwargs)
         v, f = mesh["vertices"], mesh["triangles"]
         vn = self.engine.vertex_normals(v, f)
         colors = mesh["colors"].clamp(0.0, 1.0) if "colors" in mesh else torch.ones_like(v)

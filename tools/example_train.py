@@ -26,6 +26,8 @@ def main():
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--rays", type=int, default=1024)
     ap.add_argument("--out", default=os.path.join(REPO, "gpurun_out", "example"))
+    ap.add_argument("--mesh-method", default="tetrahedra", choices=["tetrahedra", "cubes"],
+                    help="triangulation of the on-device meshes: marching tetrahedra, or the cube table (a third of the vertices and triangles)")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     dev = torch.device("cuda", 0)
@@ -74,7 +76,7 @@ def main():
     # the same surface without leaving the GPU: welded mesh, analytic normals, colours seen from a point in front of the scene
     t1 = time.perf_counter()
     m = renderer2.extract_observation_mesh(torch.tensor([0.5]), [-1, -1, -1], [1, 1, 1], resolution=256, view_point=[0.0, 0.0, -1.5], refine_steps=1,
-                                           band=True)          # the SDF is queried near the surface only
+                                           band=True, method=args.mesh_method)          # the SDF is queried near the surface only
     torch.cuda.synchronize()
     print(f"on-device mesh at 256^3: {m['vertices'].shape[0]} vertices, {m['triangles'].shape[0]} triangles, median |sdf| at the vertices "
           f"{float(m['sdf'].abs().median()) if m['sdf'].numel() else 0.0:.2e}, {time.perf_counter() - t1:.2f} s")
@@ -83,7 +85,8 @@ def main():
           f"{st['active_blocks']} of {st['blocks']} blocks ({st['seed_blocks']} seeds, {st['rounds']} growth rounds), fallback {st['fallback']}")
     # the demo's 3D number: drop the floaters, then the mean distance from a depth frame's pixels to the nearest mesh vertex.  The depth
     # frame is the synthetic scene's own (tests/synth_scene.py: a sphere of radius 0.55 + 0.08 sin(2 pi t) around (0, 0, 0.05 t))
-    clean = renderer2.extract_observation_mesh(torch.tensor([0.5]), [-1, -1, -1], [1, 1, 1], resolution=256, band=True, components=0.9)
+    clean = renderer2.extract_observation_mesh(torch.tensor([0.5]), [-1, -1, -1], [1, 1, 1], resolution=256, band=True, components=0.9,
+                                               method=args.mesh_method)
     K = torch.tensor([[800.0, 0, 319.5, 0], [0, 800.0, 255.5, 0], [0, 0, 1, 0], [0, 0, 0, 1]])
     pose = torch.eye(4)
     pose[2, 3] = -1.5
@@ -102,7 +105,7 @@ def main():
           f"{surf['mean']:.4f} (to the surface; rmse {surf['rmse']:.4f}, {100.0 * surf['within'][0]:.1f} % within 0.01)")
     # the demo's "Mesh / Texture / Normal" panels of that mesh, without a display: rasterised once on the device, shaded three times
     clean = renderer2.extract_observation_mesh(torch.tensor([0.5]), [-1, -1, -1], [1, 1, 1], resolution=256, view_point=[0.0, 0.0, -1.5], band=True,
-                                               components=0.9)
+                                               components=0.9, method=args.mesh_method)
     t1 = time.perf_counter()
     pics = renderer2.render_mesh(clean, K, pose, 512, 640, view_point=[0.0, 0.0, -1.5])
     torch.cuda.synchronize()
@@ -132,7 +135,7 @@ def main():
     from endosurf_amd.data import depth_points, read_ply, write_ply
     t1 = time.perf_counter()
     ex = renderer2.export_observation_mesh(os.path.join(args.out, "000"), torch.tensor([0.5]), [-1, -1, -1], [1, 1, 1], resolution=256,
-                                           view_point=[0.0, 0.0, -1.5], components=0.9, simplify="grid", band=True)
+                                           view_point=[0.0, 0.0, -1.5], components=0.9, simplify="grid", band=True, method=args.mesh_method)
     gt = depth_points(depth.to(dev), K, pose, 3.0)
     write_ply(os.path.join(args.out, "000_gt.ply"), gt, colors=gt_color[0][(depth > 0).to(dev)], engine=renderer2.engine)
     torch.cuda.synchronize()
