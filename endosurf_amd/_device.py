@@ -24,3 +24,19 @@ def _on_device(fn):
         with torch.cuda.device(self.device):
             return fn(self, *a, **k)
     return wrapped
+
+
+def mixed_in(mixin):
+    """Class decorator: the methods of ``mixin`` become methods of the decorated class, which keeps its list of base classes (the
+    chains of ``Engine`` and of the renderer are three and two classes long, and tests/test_module_split_host.py holds them to that).
+    A name that the class or one of its bases already defines is refused, so nothing is shadowed silently."""
+    def apply(cls):
+        for name, value in vars(mixin).items():
+            if name.startswith("__") and name.endswith("__"):
+                continue
+            for c in cls.__mro__:
+                if c is not object and name in vars(c):
+                    raise TypeError(f"{name} is defined in {c.__name__} and in {mixin.__name__}")
+            setattr(cls, name, value)
+        return cls
+    return apply

@@ -28,6 +28,13 @@ static inline int check_points(const es_points* p, bool weights, bool rows) {
     ES_REQUIRE(weights && (rows || p->M == 0), "null buffer");
     return ST_OK;
 }
+// The deformation network alone (deform.hip): explicit points only, checked before anything is launched; an empty batch launches nothing.
+static inline int check_deform_src(const es_points* p) {
+    ES_REQUIRE(p != nullptr, "es_points is null");
+    ES_REQUIRE(p->M >= 0, "negative point count");
+    ES_REQUIRE(p->mode == 0, "the deformation calls take explicit points (mode 0)");
+    return ST_OK;
+}
 static inline int check_mcolor(const es_points* pts, int flags, int m_color) {
     if (!(flags & ES_PF_COLOR) || m_color <= 0 || m_color == pts->M) return ST_OK;
     ES_REQUIRE(m_color < pts->M && m_color % 64 == 0, "m_color must be a multiple of 64 (tile aligned) or cover all points");
@@ -129,6 +136,24 @@ int es_query_sdf_rays(const es_points* pts, const float* packed, const float* we
     if (int e = check_points(pts, packed && weff, sdf_out)) return e;
     ES_REQUIRE(pts->mode == 1 && pts->n_per_ray >= 1 && ld_out >= pts->n_per_ray, "es_query_sdf_rays takes ray samples (mode 1), ld_out >= n_per_ray");
     return query_sdf(to_src(pts), packed, weff, sdf_out, use_deform, (hipStream_t)stream, ld_out, ray_done);
+}
+int es_deform_forward(const es_points* pts, const float* packed, const float* weff, float* xc_out, float* d_out, void* stream) {
+    if (int e = check_deform_src(pts)) return e;
+    if (pts->M == 0) return ST_OK;
+    ES_REQUIRE(pts->x && pts->t, "mode 0 needs x and t");
+    ES_REQUIRE(packed && weff, "null buffer");
+    ES_REQUIRE(xc_out || d_out, "es_deform_forward: both outputs are null");
+    return deform_forward(to_src(pts), packed, weff, xc_out, d_out, (hipStream_t)stream);
+}
+int es_deform_inverse(const es_points* pts, const float* init, const float* packed, const float* weff, int max_iters, float tol, float* y_out,
+                      float* step_out, int* iters_out, void* stream) {
+    if (int e = check_deform_src(pts)) return e;
+    ES_REQUIRE(max_iters >= 1, "es_deform_inverse: max_iters must be at least 1");
+    ES_REQUIRE(tol >= 0.f && tol <= 3.402823466e+38f, "es_deform_inverse: tol must be finite and not negative");          // (false for NaN)
+    if (pts->M == 0) return ST_OK;
+    ES_REQUIRE(pts->x && pts->t, "mode 0 needs x and t");
+    ES_REQUIRE(packed && weff && y_out && step_out && iters_out, "null buffer");
+    return deform_inverse(to_src(pts), init, packed, weff, max_iters, tol, y_out, step_out, iters_out, (hipStream_t)stream);
 }
 int64_t es_packed_x3_bytes(void) { return (int64_t)packed_x3_bytes(); }
 int es_pack_x3(const float* weff, void* packed_x3, int use_deform, void* stream) {

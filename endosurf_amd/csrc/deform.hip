@@ -1,0 +1,227 @@
+// The deformation network alone, no grad: D(x, t) of  x_c = x + D(x, t)  (reference DeformNetwork.forward, endosurf.py:724-738) and the
+// inverse of  y -> y + D(y, t)  by the fixed-point iteration  y_k = c - D(y_{k-1}, t)  with the per-row stopping rule of
+// endosurf_amd/tracking.py inverse_deform (DESIGN.md 7h "Row rule"), the whole iteration in ONE launch.  The evaluation is the
+// deformation half of k_query_sdf (query.hip): the same 64-point tile (32 points for small batches), LDS carve, packed weights and bias prefetch, hence the same
+// value of D per row, bit for bit, whatever the row's place in the tile and whatever its neighbours hold.  fp32 only.
+#include <cfloat>
+
+#include "chain_common.h"
+#include "encode.h"
+#include "host.h"
+#include "launch.h"
+#include "tabs.h"
+
+namespace es {
+
+// One evaluation of the deformation MLP on the tile's rows (px [3][64], pt [64]): leaves the four k-partial sums of the 3 outputs in
+// ``red`` (which aliases the encoding rows of ``aux``) behind a barrier; row r's D_i is  smalln_reduce<3>(red, i, r) + bias_i.
+// The caller puts a barrier between its last read of ``red`` and the next call.
+template <int RTC>
+__device__ __forceinline__ void deform_eval(float* mainT, float* aux, float* red, const float* px, const float* pt, const Tabs& tb,
+                                            const float4* __restrict__ packed, const float* __restrict__ weff, const QuadOff<RTC>& qo,
+                                            int tid, int lane, int wave) {
+    auto bias2 = [&](float(&b)[2], const float* __restrict__ bias) { b[0] = bias[64 * wave + (lane & 31)]; b[1] = bias[64 * wave + 32 + (lane & 31)]; };
+    encode3<6>(aux, 0, px, tid);
+    encode1<6>(aux, 39, pt, tid);
+    zero_rows(aux, 52, 56, tid);
+    __syncthreads();
+    float bc[2], bn[2];   // this layer's and the NEXT layer's bias of this lane's two columns (requested a layer ahead)
+    bias2(bn, weff + tb.boff[NET_D * LAYERS + 0]);
+    {
+        f32x16 acc[RTC][2];
+        acc_zero(acc);
+        bc[0] = bn[0]; bc[1] = bn[1];
+        bias2(bn, weff + tb.boff[NET_D * LAYERS + 1]);
+        gemm_seg<7, RTC, 2>(acc, aux, packed + tb.segoff[DF0], 0, 2 * wave, lane);
+        for_quads_off(acc, qo, 0, 2 * wave, lane, [&](int row, int col, float(&v)[4], int off, int ni) {
+            add_bias4(v, bc[ni]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = relu1(v[i]);
+            lds_store_quad_at(mainT, off, v);
+        });
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int l = 1; l <= 7; ++l) {
+        f32x16 acc[RTC][2];
+        acc_zero(acc);
+        bc[0] = bn[0]; bc[1] = bn[1];
+        if (l < 7) bias2(bn, weff + tb.boff[NET_D * LAYERS + l + 1]);
+        gemm_seg<32, RTC, 2>(acc, mainT, packed + tb.segoff[DF0 + l], 0, 2 * wave, lane);
+        __syncthreads();
+        if (l == 3 && wave == 3) {      // (wave-uniform) IDR skip: next input = [h(204) | enc(52)] (1/sqrt2 folded into W4)
+            for_quads_off(acc, qo, 0, 2 * wave, lane, [&](int row, int col, float(&v)[4], int off, int ni) {
+                if (col >= 204) {
+                    lds_load_quad(aux, col - 204, row, v);
+                } else {
+                    add_bias4(v, bc[ni]);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) v[i] = relu1(v[i]);
+                }
+                lds_store_quad_at(mainT, off, v);
+            });
+        } else {
+            for_quads_off(acc, qo, 0, 2 * wave, lane, [&](int row, int col, float(&v)[4], int off, int ni) {
+                add_bias4(v, bc[ni]);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v[i] = relu1(v[i]);
+                lds_store_quad_at(mainT, off, v);
+            });
+        }
+        __syncthreads();
+    }
+    smalln_partial<3>(mainT, weff + tb.woff[NET_D * LAYERS + 8], 256, red, tid);
+    __syncthreads();
+}
+
+// HALF: small batches run 32-point tiles as k_query_sdf's do -- the LDS tile keeps its 64-row layout, only row-tile 0 carries points,
+// every layer issues half the MFMAs and twice as many workgroups share the batch; a row's arithmetic is the same in both.
+//
+// x_c = x + D and / or D for explicit points (mode 0): the deformation block of k_query_sdf followed by a store.
+template <bool HALF>
+__global__ __launch_bounds__(NTHREADS, 2) void k_deform_forward(PointSrc src, Tabs tb, const float4* __restrict__ packed,
+                                                             const float* __restrict__ weff, float* __restrict__ xc_out,
+                                                             float* __restrict__ d_out) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* mainT = lds;
+    float* aux = lds + MAIN_FLOATS;
+    float* scr = aux + AUX56_FLOATS;
+    float* px = scr;          // [3][64]
+    float* pt = scr + 192;    // [64]
+    float* red = aux;         // [4][3][64]: aliases the encoding rows, dead by the time the last layer runs
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    constexpr int RTC = HALF ? 1 : 2;
+    constexpr int PTS = HALF ? 32 : 64;
+    const int row0 = blockIdx.x * PTS;
+    const QuadOff<RTC> qo = quad_offsets<RTC>(0, 2 * wave, lane);
+    if (tid < 64) {
+        float x[3], t, d[3];
+        load_point(src, tid < PTS ? row0 + tid : src.M, x, t, d);          // (rows past the tile's points or at or past M: zeros)
+        px[tid] = x[0]; px[64 + tid] = x[1]; px[128 + tid] = x[2]; pt[tid] = t;
+    }
+    __syncthreads();
+    deform_eval<RTC>(mainT, aux, red, px, pt, tb, packed, weff, qo, tid, lane, wave);
+    if (tid < 192) {
+        const int i = tid >> 6, row = tid & 63;
+        if (row < PTS && row0 + row < src.M) {
+            const float D = smalln_reduce<3>(red, i, row) + weff[tb.boff[NET_D * LAYERS + 8] + i];
+            const size_t o = 3 * (size_t)(row0 + row) + i;
+            if (d_out) d_out[o] = D;
+            if (xc_out) xc_out[o] = px[i * 64 + row] + D;
+        }
+    }
+}
+
+// y with y + D(y, t) = c.  The row's thread (tid < 64) keeps c, step, iters and the live flag in registers; y and t are the tile's row
+// scratch (px, pt), rewritten for live rows only.  Frozen rows (and the rows at or past M, frozen from the start) still ride through
+// the MFMAs, but none of their state changes.  Every workgroup runs at most max_iters evaluations and leaves the loop when none of its
+// own rows is live: it waits for nothing outside itself.
+template <bool HALF>
+__global__ __launch_bounds__(NTHREADS, 2) void k_deform_inverse(PointSrc src, Tabs tb, const float* __restrict__ init,
+                                                             const float4* __restrict__ packed, const float* __restrict__ weff,
+                                                             int max_iters, float tol, float* __restrict__ y_out,
+                                                             float* __restrict__ step_out, int* __restrict__ iters_out) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* mainT = lds;
+    float* aux = lds + MAIN_FLOATS;
+    float* scr = aux + AUX56_FLOATS;
+    float* px = scr;          // [3][64]: y
+    float* pt = scr + 192;    // [64]
+    float* red = aux;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    constexpr int RTC = HALF ? 1 : 2;
+    constexpr int PTS = HALF ? 32 : 64;
+    const int row0 = blockIdx.x * PTS;
+    const QuadOff<RTC> qo = quad_offsets<RTC>(0, 2 * wave, lane);
+    const bool mine = tid < PTS && row0 + tid < src.M;          // this thread owns a row of the batch
+    float c0 = 0.f, c1 = 0.f, c2 = 0.f, step = 0.f;
+    int iters = 0, live = mine ? 1 : 0;
+    if (tid < 64) {
+        float x[3], t, d[3];
+        load_point(src, tid < PTS ? row0 + tid : src.M, x, t, d);
+        c0 = x[0]; c1 = x[1]; c2 = x[2];
+        float y[3] = {c0, c1, c2};
+        if (mine && init != nullptr) {
+            const size_t o = 3 * (size_t)(row0 + tid);
+            y[0] = init[o]; y[1] = init[o + 1]; y[2] = init[o + 2];
+        }
+        px[tid] = y[0]; px[64 + tid] = y[1]; px[128 + tid] = y[2]; pt[tid] = t;
+    }
+    __syncthreads();
+    const int b8 = tb.boff[NET_D * LAYERS + 8];
+    for (int k = 1; k <= max_iters; ++k) {
+        deform_eval<RTC>(mainT, aux, red, px, pt, tb, packed, weff, qo, tid, lane, wave);
+        if (live) {          // (tid < PTS and the row is in the batch)
+            const float c[3] = {c0, c1, c2};
+            float yn[3], e[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const float D = smalln_reduce<3>(red, i, tid) + weff[b8 + i];
+                yn[i] = c[i] - D;
+                e[i] = yn[i] - px[i * 64 + tid];
+            }
+            // the twin's sum of squares, product by product (no contraction into fused multiply-adds)
+            const float s = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(e[0], e[0]), __fmul_rn(e[1], e[1])), __fmul_rn(e[2], e[2])));
+            const bool ok = s <= FLT_MAX;          // (false for inf and nan: the update is refused)
+            if (ok) { px[tid] = yn[0]; px[64 + tid] = yn[1]; px[128 + tid] = yn[2]; }
+            step = ok ? s : FLT_MAX;
+            iters = k;
+            live = ok && !(tol > 0.f && s <= tol);
+        }
+        // workgroup-uniform exit; also the barrier between this round's reads of ``red`` / writes of px and the next encoding
+        if (!__syncthreads_or(live)) break;
+    }
+    if (mine) {
+        const size_t o = 3 * (size_t)(row0 + tid);
+        y_out[o] = px[tid]; y_out[o + 1] = px[64 + tid]; y_out[o + 2] = px[128 + tid];
+        step_out[row0 + tid] = step;
+        iters_out[row0 + tid] = iters;
+    }
+}
+
+static int deform_attrs() {
+    static DeviceOnce attr_done;
+    if (attr_done.first()) {
+        if (int e = allow_big_lds(k_deform_forward<false>, LEAN_LDS_BYTES)) return e;
+        if (int e = allow_big_lds(k_deform_forward<true>, LEAN_LDS_BYTES)) return e;
+        if (int e = allow_big_lds(k_deform_inverse<false>, LEAN_LDS_BYTES)) return e;
+        if (int e = allow_big_lds(k_deform_inverse<true>, LEAN_LDS_BYTES)) return e;
+        attr_done.done();
+    }
+    return ST_OK;
+}
+
+// 32-point tiles up to this many rows, 64-point tiles above.  Measured: the inverse at 2 630 rows 0.83 against 1.49 ms, at
+// 8 192 1.09 against 1.87, at 16 384 1.39 against 1.54; at 32 768 the forward is 5 % faster on 64-point tiles and the inverse within 3 %.
+constexpr int DEFORM_HALF_MAX_ROWS = 16384;
+
+int deform_forward(const PointSrc& src, const float* packed, const float* weff, float* xc_out, float* d_out, hipStream_t st) {
+    if (src.M <= 0) return ST_OK;
+    if (int e = deform_attrs()) return e;
+    const bool half = src.M <= DEFORM_HALF_MAX_ROWS;
+    const int pts = half ? 32 : 64;
+    const dim3 grid((src.M + pts - 1) / pts), block(NTHREADS);
+    const float4* pk = reinterpret_cast<const float4*>(packed);
+    if (half) hipLaunchKernelGGL(k_deform_forward<true>, grid, block, LEAN_LDS_BYTES, st, src, make_tabs(), pk, weff, xc_out, d_out);
+    else hipLaunchKernelGGL(k_deform_forward<false>, grid, block, LEAN_LDS_BYTES, st, src, make_tabs(), pk, weff, xc_out, d_out);
+    return hip_last("deform_forward");
+}
+
+int deform_inverse(const PointSrc& src, const float* init, const float* packed, const float* weff, int max_iters, float tol, float* y_out,
+                   float* step_out, int* iters_out, hipStream_t st) {
+    if (src.M <= 0) return ST_OK;
+    if (int e = deform_attrs()) return e;
+    const bool half = src.M <= DEFORM_HALF_MAX_ROWS;
+    const int pts = half ? 32 : 64;
+    const dim3 grid((src.M + pts - 1) / pts), block(NTHREADS);
+    const float4* pk = reinterpret_cast<const float4*>(packed);
+    if (half) hipLaunchKernelGGL(k_deform_inverse<true>, grid, block, LEAN_LDS_BYTES, st, src, make_tabs(), init, pk, weff, max_iters, tol, y_out,
+                                 step_out, iters_out);
+    else hipLaunchKernelGGL(k_deform_inverse<false>, grid, block, LEAN_LDS_BYTES, st, src, make_tabs(), init, pk, weff, max_iters, tol, y_out,
+                            step_out, iters_out);
+    return hip_last("deform_inverse");
+}
+
+}  // namespace es

@@ -35,6 +35,11 @@ size_t packed_x3_bytes();
 int pack_x3(const float* weff, void* packed_x3, int use_deform, hipStream_t st);
 int query_sdf_x3(const PointSrc& src, const void* packed_x3, const float* weff, float* sdf_out, int use_deform, hipStream_t st, int ld_out, const int* ray_done);
 
+// deform.hip
+int deform_forward(const PointSrc& src, const float* packed, const float* weff, float* xc_out, float* d_out, hipStream_t st);
+int deform_inverse(const PointSrc& src, const float* init, const float* packed, const float* weff, int max_iters, float tol, float* y_out,
+                   float* step_out, int* iters_out, hipStream_t st);
+
 // point_fwd.hip, point_bwd.hip
 int point_forward(const PointSrc& src, const float* packed, const float* weff, float* ws, int flags, int m_color, hipStream_t st,
                   const void* packed_x3 = nullptr);

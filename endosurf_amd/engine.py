@@ -9,10 +9,11 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._device import f32, u8  # noqa: F401  (importable from here as before)
+from ._device import f32, mixed_in, u8  # noqa: F401  (f32, u8: importable from here as before)
 from ._lib import check, es_composite_args, es_points, ptr, stream_ptr
 from .engine_eval import EvalMixin
 from .engine_mesh import MeshMixin
+from .engine_track import TrackMixin
 
 
 class PointCtx:
@@ -35,6 +36,7 @@ class PointCtx:
         return v
 
 
+@mixed_in(TrackMixin)
 class Engine(MeshMixin, EvalMixin):
     """Per-device handle (stateless apart from the loaded library): step and render launches here, geometry and evaluation in the mixins."""
 
@@ -182,7 +184,13 @@ class Engine(MeshMixin, EvalMixin):
     # ---- point sources ----------------------------------------------------------------------------
     @staticmethod
     def points(x=None, t=None, dirs=None, rays=None, z=None, n_per_ray=1, ldz=None, M=None) -> es_points:
-        """mode 0: explicit (x, t[, dirs]); mode 1: ray samples (rays, z); mode 2: ray samples followed by explicit (x, t)."""
+        """mode 0: explicit (x, t[, dirs]); mode 1: ray samples (rays, z); mode 2: ray samples followed by explicit (x, t).
+        Every tensor must live on a GPU: the kernels read these addresses as they are, and a host address there is a memory fault,
+        not an error message -- so it is refused here, before any pointer is taken and before anything is launched."""
+        for name, v in (("x", x), ("t", t), ("dirs", dirs), ("rays", rays), ("z", z)):
+            if torch.is_tensor(v) and not v.is_cuda:
+                raise ValueError(f"Engine.points: {name} is on {v.device}; a point source takes device tensors only "
+                                 f"(move it with .to(device) first)")
         p = es_points()
         if rays is not None:
             p.rays, p.z = ptr(rays), ptr(z)

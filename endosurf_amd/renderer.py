@@ -7,7 +7,7 @@ Same constructor (``render_cfg``, ``net_cfg``, ``device``), same public methods 
 every tensor op of the hot path runs inside the C-ABI library; there is no PyTorch/CPU fallback.
 
 The parameter container and the reference-named modules live in ``model``, the autograd functions in ``functions``, the rows a
-render keeps for the calls that follow it in ``tail``, the offline geometry methods in ``renderer_mesh``; this module is the render
+render keeps for the calls that follow it in ``tail``, the offline geometry methods in ``renderer_mesh``, the surface tracks in ``renderer_track``; this module is the render
 path, frame evaluation and the policy of the tail.
 """
 from __future__ import annotations
@@ -20,15 +20,17 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._device import _on_device
+from ._device import _on_device, mixed_in
 from .engine import Engine, f32
 from .functions import _EodLossFn, _PackFn, _PointEvalFn, _RenderFn, _SnLossFn, _SValFn
 from .model import EndoSurfNet, WNLinear, _check_arch, _reference_style_init  # noqa: F401  (the last two: importable from here as before)
 from .renderer_mesh import RendererMeshMixin
+from .renderer_track import RendererTrackMixin
 from .tail import _Lazy, _LazyEodFn, _PendingEod, _Tail, _TailEvalFn
 
 
 # ---------------------------------------------------------------------------------------------------------------
+@mixed_in(RendererTrackMixin)
 class EndoSurfRenderer(RendererMeshMixin, nn.Module):
     """EndoSurf renderer (drop-in for reference src/renderer/endosurf.py:14-521)."""
 
@@ -721,7 +723,7 @@ class EndoSurfRenderer(RendererMeshMixin, nn.Module):
     def sdf_observed(self, pts, t):
         """get_sdf_from_observed_space (endosurf.py:570-579) for [M,3] points and [M] / scalar time, no grad."""
         weff, packed = self._weights()
-        x = f32(pts)
-        tt = f32(t).reshape(-1)
+        x = f32(torch.as_tensor(pts).to(device=self.device, dtype=torch.float32))
+        tt = f32(torch.as_tensor(t).to(device=self.device, dtype=torch.float32)).reshape(-1)
         with torch.no_grad():
             return self.engine.query_sdf(self.engine.points(x=x, t=tt), weff.detach(), packed, self.use_deform).view(-1, 1)

@@ -1,4 +1,4 @@
-"""Surface tracks on the host: the deformation map inverted, points and meshes followed through time.
+"""Surface tracks: the deformation map inverted, points and meshes followed through time.
 
 The model is a canonical SDF and a deformation x_c = x + D(x, t); two observed points are the same piece of tissue exactly when they
 map to the same canonical point.  The package evaluates the forward direction only; this module adds the inverse, as the fixed-point
@@ -6,8 +6,10 @@ iteration y_k = c - D(y_{k-1}, t) with a per-row stopping rule, and composes it 
 and per-vertex correspondence over a sequence of times, where ``extract_observation_mesh`` gives an unrelated mesh per frame.  Plain torch
 in the dtype and on the device of its inputs; ``deform_fn(y, t) -> D`` is any callable on [M,3] points and [M] times, e.g. the fp64
 oracle's ``lambda y, t: net.deform(y, t, with_jac=False)[0]`` (a model's ``deform_network`` has that signature for device tensors, a full
-point evaluation per call; no GPU test covers the combination yet).  ``inverse_deform`` is also the written specification, row rule included, of a device kernel that runs the whole
-iteration in one launch; that kernel is not in the tree yet.
+point evaluation per call).  ``inverse_deform`` is also the written specification, row rule included, of the device kernel that runs the
+whole iteration in one launch (csrc/deform.hip): the functions that solve take ``inverse=``, a callable
+``(c, t, init, max_iters, tol) -> (y, step, iters)`` that replaces ``inverse_deform`` over ``deform_fn``, and the renderer's methods of
+the same names (``renderer_track``) pass that kernel there.
 
 Contract: where D(., t) has a Lipschitz constant rho < 1 the inverse exists, is unique, and the iteration converges to it
 from any start, |y_k - y*| <= rho^k / (1 - rho) |y_1 - y_0|.  Where rho >= 1 the surface folds and nothing is promised: such a row comes
@@ -63,6 +65,13 @@ def inverse_deform(deform_fn, c, t, init=None, max_iters=64, tol=1e-6):
     return y, step, iters
 
 
+def _solver(deform_fn, inverse):
+    """``inverse`` as given, or ``inverse_deform`` over ``deform_fn`` when it is None: (c, t, init, max_iters, tol) -> (y, step, iters)."""
+    if inverse is not None:
+        return inverse
+    return lambda c, t, init, max_iters, tol: inverse_deform(deform_fn, c, t, init, max_iters, tol)
+
+
 def _result(y, step, iters, tol):
     return {"points": y, "step": step, "iters": iters, "converged": step <= tol}
 
@@ -73,17 +82,17 @@ def to_canonical(deform_fn, points, t):
     return points + deform_fn(points, _times(t, points.shape[0], points))
 
 
-def to_observed(deform_fn, canonical, t, init=None, max_iters=64, tol=1e-6):
+def to_observed(deform_fn, canonical, t, init=None, max_iters=64, tol=1e-6, inverse=None):
     """The observed positions at ``t`` of canonical points: dict(points, step, iters, converged)."""
-    return _result(*inverse_deform(deform_fn, canonical, t, init, max_iters, tol), float(tol))
+    return _result(*_solver(deform_fn, inverse)(canonical, t, init, max_iters, tol), float(tol))
 
 
-def warp_points(deform_fn, points, t_from, t_to, init=None, max_iters=64, tol=1e-6):
+def warp_points(deform_fn, points, t_from, t_to, init=None, max_iters=64, tol=1e-6, inverse=None):
     """Where the tissue seen at ``points`` at ``t_from`` is at ``t_to``: to_observed(to_canonical(points, t_from), t_to)."""
-    return to_observed(deform_fn, to_canonical(deform_fn, points, t_from), t_to, init, max_iters, tol)
+    return to_observed(deform_fn, to_canonical(deform_fn, points, t_from), t_to, init, max_iters, tol, inverse)
 
 
-def track_points(deform_fn, points, t_from, times, warm_start=False, max_iters=64, tol=1e-6):
+def track_points(deform_fn, points, t_from, times, warm_start=False, max_iters=64, tol=1e-6, inverse=None):
     """``points`` [P,3] seen at ``t_from`` followed through ``times`` [F]: dict(points [F,P,3], canonical [P,3], step, iters, converged
     [F,P]).  ``warm_start=False``: all F*P rows in one solve with a time per row, every row starting from its canonical point.
     ``warm_start=True``: the frames in the given order, frame f starting from frame f-1's solution and the first from ``points``."""
@@ -92,24 +101,25 @@ def track_points(deform_fn, points, t_from, times, warm_start=False, max_iters=6
     times = torch.as_tensor(times, dtype=points.dtype, device=points.device).reshape(-1)
     F = times.numel()
     canon = to_canonical(deform_fn, points, t_from)
+    solve = _solver(deform_fn, inverse)
     if not warm_start:
-        y, step, iters = inverse_deform(deform_fn, canon.repeat(F, 1), times.repeat_interleave(P), None, max_iters, tol)
+        y, step, iters = solve(canon.repeat(F, 1), times.repeat_interleave(P), None, max_iters, tol)
         y, step, iters = y.reshape(F, P, 3), step.reshape(F, P), iters.reshape(F, P)
     else:
         ys, steps, its, start = [], [], [], points
         for f in range(F):
-            start, s, i = inverse_deform(deform_fn, canon, times[f], start, max_iters, tol)
+            start, s, i = solve(canon, times[f], start, max_iters, tol)
             ys.append(start), steps.append(s), its.append(i)
         stack = lambda a, shape, dt: torch.stack(a) if a else torch.zeros(shape, dtype=dt, device=points.device)
         y, step, iters = stack(ys, (0, P, 3), points.dtype), stack(steps, (0, P), points.dtype), stack(its, (0, P), torch.int32)
     return {"points": y, "canonical": canon, "step": step, "iters": iters, "converged": step <= float(tol)}
 
 
-def track_mesh(deform_fn, vertices, triangles, t, times, warm_start=True, max_iters=64, tol=1e-6):
+def track_mesh(deform_fn, vertices, triangles, t, times, warm_start=True, max_iters=64, tol=1e-6, inverse=None):
     """The mesh (vertices [V,3] at time ``t``, triangles) carried through ``times``: one triangle list -- the object passed in -- and
     per-vertex correspondence: dict(vertices [F,V,3], triangles, canonical [V,3], displacement [F,V] = the distance from the source
     vertex, step, iters, converged [F,V])."""
-    tr = track_points(deform_fn, vertices, t, times, warm_start, max_iters, tol)
+    tr = track_points(deform_fn, vertices, t, times, warm_start, max_iters, tol, inverse)
     v = tr.pop("points")
     disp = torch.sqrt(((v - torch.as_tensor(vertices)[None]) ** 2).sum(-1))
     return {"vertices": v, "triangles": triangles, "displacement": disp, **tr}
