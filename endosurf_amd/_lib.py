@@ -64,6 +64,8 @@ PROTOTYPES = {
     "es_query_sdf_tiles": (C.c_int, [C.POINTER(es_points), _c_float_p, _c_float_p, _c_float_p, C.c_int, C.c_int, C.c_void_p]),
     "es_deform_forward": (_I, [C.POINTER(es_points), _P, _P, _P, _P, _P]),
     "es_deform_inverse": (_I, [C.POINTER(es_points), _P, _P, _P, _I, _F, _P, _P, _P, _P]),
+    "es_deform_jacobian": (_I, [C.POINTER(es_points), _P, _P, _P, _P, _P]),
+    "es_strain_rows": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "es_packed_x3_bytes": (C.c_int64, []),
     "es_pack_x3": (_I, [_P, _P, _I, _P]),
     "es_query_sdf_x3": (_I, [C.POINTER(es_points), _P, _P, _P, _I, _P, _I, _P]),

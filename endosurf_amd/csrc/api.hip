@@ -155,6 +155,23 @@ int es_deform_inverse(const es_points* pts, const float* init, const float* pack
     ES_REQUIRE(packed && weff && y_out && step_out && iters_out, "null buffer");
     return deform_inverse(to_src(pts), init, packed, weff, max_iters, tol, y_out, step_out, iters_out, (hipStream_t)stream);
 }
+int es_deform_jacobian(const es_points* pts, const float* packed, const float* weff, float* jac_out, float* xc_out, void* stream) {
+    if (int e = check_deform_src(pts)) return e;
+    if (pts->M == 0) return ST_OK;
+    ES_REQUIRE(pts->x && pts->t, "mode 0 needs x and t");
+    ES_REQUIRE(packed && weff, "null buffer");
+    ES_REQUIRE(jac_out || xc_out, "es_deform_jacobian: both outputs are null");
+    return deform_jacobian(to_src(pts), packed, weff, jac_out, xc_out, (hipStream_t)stream);
+}
+int es_strain_rows(const float* jac_from, const float* jac_to, const float* normals, int M, float* F_out, float* det_out, float* stretch_out,
+                   float* area_out, float* surface_out, unsigned char* valid_out, void* stream) {
+    ES_REQUIRE(M >= 0, "negative row count");
+    if (M == 0) return ST_OK;
+    ES_REQUIRE(jac_to, "null buffer");
+    ES_REQUIRE(F_out || det_out || stretch_out || area_out || surface_out || valid_out, "es_strain_rows: every output is null");
+    ES_REQUIRE(normals || !(area_out || surface_out), "es_strain_rows: the surface outputs need normals");
+    return strain_rows(jac_from, jac_to, normals, M, F_out, det_out, stretch_out, area_out, surface_out, valid_out, (hipStream_t)stream);
+}
 int64_t es_packed_x3_bytes(void) { return (int64_t)packed_x3_bytes(); }
 int es_pack_x3(const float* weff, void* packed_x3, int use_deform, void* stream) {
     ES_REQUIRE(weff && packed_x3, "null buffer");

@@ -40,6 +40,11 @@ int deform_forward(const PointSrc& src, const float* packed, const float* weff, 
 int deform_inverse(const PointSrc& src, const float* init, const float* packed, const float* weff, int max_iters, float tol, float* y_out,
                    float* step_out, int* iters_out, hipStream_t st);
 
+// deform_jac.hip, strain.hip
+int deform_jacobian(const PointSrc& src, const float* packed, const float* weff, float* jac_out, float* xc_out, hipStream_t st);
+int strain_rows(const float* jac_from, const float* jac_to, const float* normals, int M, float* F_out, float* det_out, float* stretch_out,
+                float* area_out, float* surface_out, unsigned char* valid_out, hipStream_t st);
+
 // point_fwd.hip, point_bwd.hip
 int point_forward(const PointSrc& src, const float* packed, const float* weff, float* ws, int flags, int m_color, hipStream_t st,
                   const void* packed_x3 = nullptr);

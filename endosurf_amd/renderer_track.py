@@ -1,10 +1,12 @@
 """The surface tracks of ``renderer.EndoSurfRenderer`` (a mixin): ``tracking``'s functions with the model's own deformation network
-under them -- D(x, t) in one launch of the deformation network alone, the inverse as one launch per solve (csrc/deform.hip)."""
+under them -- D(x, t) in one launch of the deformation network alone, the inverse as one launch per solve (csrc/deform.hip) -- and
+``strain``'s functions likewise: the Jacobian of the deformation in one launch (csrc/deform_jac.hip), the per-row algebra in another
+(csrc/strain.hip)."""
 from __future__ import annotations
 
 import torch
 
-from . import tracking
+from . import strain, tracking
 from ._device import _on_device, f32
 
 # The default stopping length of the device solver, where the host twin's fp64 default is 1e-6: fp32 evaluation noise of D is of order
@@ -111,3 +113,50 @@ class RendererTrackMixin:
         with torch.no_grad():
             return tracking.track_mesh(self.deform, self._track_rows(vertices), triangles, t, times, warm_start, max_iters, tol,
                                        inverse=self._track_solver())
+
+    # ---- strain along the tracks (strain.py) -----------------------------------------------------------------------------
+    @_on_device
+    def deform_jacobian(self, pts, t):
+        """J(x, t) = I + dD/dx [M,3,3] (dim_out, dim_in) for [M,3] points and [M] / scalar time, no grad: ``strain``'s ``jacobian_fn``,
+        one launch (csrc/deform_jac.hip).  Identities, and no launch, without a deformation network."""
+        x = self._track_rows(pts)
+        M = x.shape[0]
+        tt = self._track_times(t, M)
+        if not self.use_deform or M == 0:
+            return torch.eye(3, device=self.device).expand(M, 3, 3).contiguous()
+        weff, packed = self._weights()
+        with torch.no_grad():
+            return self.engine.deform_jacobian(self.engine.points(x=x, t=tt), weff.detach(), packed)
+
+    def _strain_rows(self, jac_from, jac_to, normals):
+        """``strain``'s ``rows_fn=``: the per-row algebra in one launch (csrc/strain.hip), no read-back."""
+        return self.engine.strain_rows(None if jac_from is None else self._track_rows(jac_from, 9).reshape(-1, 3, 3),
+                                       self._track_rows(jac_to, 9).reshape(-1, 3, 3), None if normals is None else self._track_rows(normals))
+
+    @_on_device
+    def track_strain(self, points_from, t_from, points_to, t_to, normals=None):
+        """The strain of the tissue between the two ends of track rows (``strain.track_strain``: F, det, stretch, valid and, with
+        ``normals`` at the "from" end, area and surface_stretch; device tensors, no read-back): ``points_from`` at ``t_from`` and
+        ``points_to`` at ``t_to`` are the same tissue, e.g. ``pts`` and ``warp_points(pts, t_from, t_to)["points"]``.
+        ``points_from=None``: relative to the canonical shape.  One Jacobian launch per end and one strain launch."""
+        with torch.no_grad():
+            return strain.track_strain(self.deform_jacobian, None if points_from is None else self._track_rows(points_from), t_from,
+                                       self._track_rows(points_to), t_to, None if normals is None else self._track_rows(normals),
+                                       rows_fn=self._strain_rows)
+
+    @_on_device
+    def mesh_strain(self, track, times, reference=0, normals=None):
+        """The strain maps of a tracked mesh (``strain.mesh_strain`` on the dict ``track_mesh`` returns, over the same ``times``):
+        every frame against frame ``reference`` or against ``"canonical"``, every output [F,V,...] on the device.  One Jacobian launch
+        for all F*V rows (a time per row) and one strain launch; the default normals are ``Engine.vertex_normals`` of the reference
+        vertices and the track's triangles."""
+        dev = {"vertices": f32(torch.as_tensor(track["vertices"]).to(device=self.device, dtype=torch.float32)),
+               "converged": torch.as_tensor(track["converged"]).to(self.device),
+               "triangles": track["triangles"]}
+        if isinstance(reference, str):
+            dev["canonical"] = self._track_rows(track["canonical"])
+        times = f32(torch.as_tensor(times).to(device=self.device, dtype=torch.float32)).reshape(-1)
+        normals_fn = lambda v, tri: self.engine.vertex_normals(self._track_rows(v), torch.as_tensor(tri).to(self.device))
+        with torch.no_grad():
+            return strain.mesh_strain(self.deform_jacobian, dev, times, reference, None if normals is None else self._track_rows(normals),
+                                      normals_fn=normals_fn, rows_fn=self._strain_rows)
