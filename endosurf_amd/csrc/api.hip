@@ -172,6 +172,22 @@ int es_strain_rows(const float* jac_from, const float* jac_to, const float* norm
     ES_REQUIRE(normals || !(area_out || surface_out), "es_strain_rows: the surface outputs need normals");
     return strain_rows(jac_from, jac_to, normals, M, F_out, det_out, stretch_out, area_out, surface_out, valid_out, (hipStream_t)stream);
 }
+int es_trace_surface(const float* rays, int N, float tau, float eps, float relax, float min_step, int max_iters, int tile_points,
+                     const float* packed, const float* weff, int use_deform, float* depth_out, int* status_out, int* iters_out,
+                     float* residual_out, float* points_out, void* stream) {
+    constexpr float FMAX = 3.402823466e+38f;          // (each comparison is false for NaN)
+    ES_REQUIRE(N >= 0, "es_trace_surface: N must not be negative");
+    ES_REQUIRE(tau >= -FMAX && tau <= FMAX, "es_trace_surface: tau must be finite");
+    ES_REQUIRE(eps >= 0.f && eps <= FMAX, "es_trace_surface: eps must be finite and not negative");
+    ES_REQUIRE(relax > 0.f && relax <= 1.f, "es_trace_surface: relax must be in (0, 1]");
+    ES_REQUIRE(min_step > 0.f && min_step <= FMAX, "es_trace_surface: min_step must be finite and positive");
+    ES_REQUIRE(max_iters >= 1 && max_iters <= ES_TRACE_MAX_ITERS, "es_trace_surface: max_iters must be in [1, 1024]");
+    ES_REQUIRE(tile_points == 0 || tile_points == 32 || tile_points == 64, "es_trace_surface: tile_points: 0 (the library's choice), 32 or 64");
+    if (N == 0) return ST_OK;
+    ES_REQUIRE(rays && packed && weff && depth_out && status_out, "es_trace_surface: null buffer (rays, packed, weff, depth_out, status_out)");
+    return trace_surface(rays, N, tau, eps, relax, min_step, max_iters, tile_points, packed, weff, use_deform, depth_out, status_out, iters_out,
+                         residual_out, points_out, (hipStream_t)stream);
+}
 int64_t es_packed_x3_bytes(void) { return (int64_t)packed_x3_bytes(); }
 int es_pack_x3(const float* weff, void* packed_x3, int use_deform, void* stream) {
     ES_REQUIRE(weff && packed_x3, "null buffer");

@@ -40,6 +40,11 @@ int deform_forward(const PointSrc& src, const float* packed, const float* weff, 
 int deform_inverse(const PointSrc& src, const float* init, const float* packed, const float* weff, int max_iters, float tol, float* y_out,
                    float* step_out, int* iters_out, hipStream_t st);
 
+// trace.hip
+int trace_surface(const float* rays, int N, float tau, float eps, float relax, float min_step, int max_iters, int tile_points,
+                  const float* packed, const float* weff, int use_deform, float* depth_out, int* status_out, int* iters_out,
+                  float* residual_out, float* points_out, hipStream_t st);
+
 // deform_jac.hip, strain.hip
 int deform_jacobian(const PointSrc& src, const float* packed, const float* weff, float* jac_out, float* xc_out, hipStream_t st);
 int strain_rows(const float* jac_from, const float* jac_to, const float* normals, int M, float* F_out, float* det_out, float* stretch_out,

@@ -13,6 +13,7 @@ from ._device import f32, mixed_in, u8  # noqa: F401  (f32, u8: importable from 
 from ._lib import check, es_composite_args, es_points, ptr, stream_ptr
 from .engine_eval import EvalMixin
 from .engine_mesh import MeshMixin
+from .engine_trace import TraceMixin
 from .engine_track import TrackMixin
 
 
@@ -36,6 +37,7 @@ class PointCtx:
         return v
 
 
+@mixed_in(TraceMixin)
 @mixed_in(TrackMixin)
 class Engine(MeshMixin, EvalMixin):
     """Per-device handle (stateless apart from the loaded library): step and render launches here, geometry and evaluation in the mixins."""

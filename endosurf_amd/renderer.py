@@ -7,7 +7,7 @@ Same constructor (``render_cfg``, ``net_cfg``, ``device``), same public methods 
 every tensor op of the hot path runs inside the C-ABI library; there is no PyTorch/CPU fallback.
 
 The parameter container and the reference-named modules live in ``model``, the autograd functions in ``functions``, the rows a
-render keeps for the calls that follow it in ``tail``, the offline geometry methods in ``renderer_mesh``, the surface tracks in ``renderer_track``; this module is the render
+render keeps for the calls that follow it in ``tail``, the offline geometry methods in ``renderer_mesh``, the surface tracks in ``renderer_track``, surface tracing in ``renderer_trace``; this module is the render
 path, frame evaluation and the policy of the tail.
 """
 from __future__ import annotations
@@ -25,11 +25,13 @@ from .engine import Engine, f32
 from .functions import _EodLossFn, _PackFn, _PointEvalFn, _RenderFn, _SnLossFn, _SValFn
 from .model import EndoSurfNet, WNLinear, _check_arch, _reference_style_init  # noqa: F401  (the last two: importable from here as before)
 from .renderer_mesh import RendererMeshMixin
+from .renderer_trace import RendererTraceMixin
 from .renderer_track import RendererTrackMixin
 from .tail import _Lazy, _LazyEodFn, _PendingEod, _Tail, _TailEvalFn
 
 
 # ---------------------------------------------------------------------------------------------------------------
+@mixed_in(RendererTraceMixin)
 @mixed_in(RendererTrackMixin)
 class EndoSurfRenderer(RendererMeshMixin, nn.Module):
     """EndoSurf renderer (drop-in for reference src/renderer/endosurf.py:14-521)."""
