@@ -1,38 +1,31 @@
 // The deformation network alone, no grad: D(x, t) of  x_c = x + D(x, t)  (reference DeformNetwork.forward, endosurf.py:724-738) and the
 // inverse of  y -> y + D(y, t)  by the fixed-point iteration  y_k = c - D(y_{k-1}, t)  with the per-row stopping rule of
-// endosurf_amd/tracking.py inverse_deform (DESIGN.md 7h "Row rule"), the whole iteration in ONE launch.  The evaluation is the
-// deformation half of k_query_sdf (query.hip): the same 64-point tile (32 points for small batches), LDS carve, packed weights and bias prefetch, hence the same
-// value of D per row, bit for bit, whatever the row's place in the tile and whatever its neighbours hold.  fp32 only.
+// endosurf_amd/tracking.py inverse_deform (DESIGN.md 7h "Row rule"), the whole iteration in ONE launch.  The evaluation is
+// deform_eval (field_eval.h), the body k_query_sdf (query.hip) runs for its deformation half on the same tile: hence the same value of
+// D per row, bit for bit, whatever the row's place in the tile and whatever its neighbours hold.  fp32 only.
 #include <cfloat>
 
 #include "chain_common.h"
-#include "deform_eval.h"
 #include "encode.h"
+#include "field_eval.h"
 #include "host.h"
 #include "launch.h"
 #include "tabs.h"
 
 namespace es {
 
-// HALF: small batches run 32-point tiles as k_query_sdf's do -- the LDS tile keeps its 64-row layout, only row-tile 0 carries points,
-// every layer issues half the MFMAs and twice as many workgroups share the batch; a row's arithmetic is the same in both.
-//
-// x_c = x + D and / or D for explicit points (mode 0): the deformation block of k_query_sdf followed by a store.
+// x_c = x + D and / or D for explicit points (mode 0): k_query_sdf's prologue and deformation half followed by a store.  HALF: small
+// batches run 32-point tiles (LeanTile, field_eval.h).
 template <bool HALF>
 __global__ __launch_bounds__(NTHREADS, 2) void k_deform_forward(PointSrc src, Tabs tb, const float4* __restrict__ packed,
                                                              const float* __restrict__ weff, float* __restrict__ xc_out,
                                                              float* __restrict__ d_out) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* mainT = lds;
-    float* aux = lds + MAIN_FLOATS;
-    float* scr = aux + AUX56_FLOATS;
-    float* px = scr;          // [3][64]
-    float* pt = scr + 192;    // [64]
-    float* red = aux;         // [4][3][64]: aliases the encoding rows, dead by the time the last layer runs
+    using Tile = LeanTile<HALF>;
+    constexpr int RTC = Tile::RTC, PTS = Tile::PTS;
+    float *mainT = lds + Tile::MAIN, *aux = lds + Tile::AUX, *red = lds + Tile::RED, *px = lds + Tile::PX, *pt = lds + Tile::PT;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    constexpr int RTC = HALF ? 1 : 2;
-    constexpr int PTS = HALF ? 32 : 64;
     const int row0 = blockIdx.x * PTS;
     const QuadOff<RTC> qo = quad_offsets<RTC>(0, 2 * wave, lane);
     if (tid < 64) {
@@ -63,16 +56,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_deform_inverse(PointSrc src, Ta
                                                              int max_iters, float tol, float* __restrict__ y_out,
                                                              float* __restrict__ step_out, int* __restrict__ iters_out) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* mainT = lds;
-    float* aux = lds + MAIN_FLOATS;
-    float* scr = aux + AUX56_FLOATS;
-    float* px = scr;          // [3][64]: y
-    float* pt = scr + 192;    // [64]
-    float* red = aux;
+    using Tile = LeanTile<HALF>;
+    constexpr int RTC = Tile::RTC, PTS = Tile::PTS;
+    float *mainT = lds + Tile::MAIN, *aux = lds + Tile::AUX, *red = lds + Tile::RED, *px = lds + Tile::PX, *pt = lds + Tile::PT;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    constexpr int RTC = HALF ? 1 : 2;
-    constexpr int PTS = HALF ? 32 : 64;
     const int row0 = blockIdx.x * PTS;
     const QuadOff<RTC> qo = quad_offsets<RTC>(0, 2 * wave, lane);
     const bool mine = tid < PTS && row0 + tid < src.M;          // this thread owns a row of the batch
@@ -121,46 +109,35 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_deform_inverse(PointSrc src, Ta
     }
 }
 
-static int deform_attrs() {
-    static DeviceOnce attr_done;
-    if (attr_done.first()) {
-        if (int e = allow_big_lds(k_deform_forward<false>, LEAN_LDS_BYTES)) return e;
-        if (int e = allow_big_lds(k_deform_forward<true>, LEAN_LDS_BYTES)) return e;
-        if (int e = allow_big_lds(k_deform_inverse<false>, LEAN_LDS_BYTES)) return e;
-        if (int e = allow_big_lds(k_deform_inverse<true>, LEAN_LDS_BYTES)) return e;
-        attr_done.done();
-    }
-    return ST_OK;
-}
-
 // 32-point tiles up to this many rows, 64-point tiles above.  Measured: the inverse at 2 630 rows 0.83 against 1.49 ms, at
 // 8 192 1.09 against 1.87, at 16 384 1.39 against 1.54; at 32 768 the forward is 5 % faster on 64-point tiles and the inverse within 3 %.
 constexpr int DEFORM_HALF_MAX_ROWS = 16384;
 
 int deform_forward(const PointSrc& src, const float* packed, const float* weff, float* xc_out, float* d_out, hipStream_t st) {
     if (src.M <= 0) return ST_OK;
-    if (int e = deform_attrs()) return e;
+    static constexpr decltype(&k_deform_forward<false>) KERNELS[] = {k_deform_forward<false>, k_deform_forward<true>};          // [HALF]
+    static DeviceOnce attr_done;
+    if (int e = allow_big_lds_once(attr_done, KERNELS, LEAN_LDS_BYTES)) return e;
     const bool half = src.M <= DEFORM_HALF_MAX_ROWS;
     const int pts = half ? 32 : 64;
     const dim3 grid((src.M + pts - 1) / pts), block(NTHREADS);
     const float4* pk = reinterpret_cast<const float4*>(packed);
-    if (half) hipLaunchKernelGGL(k_deform_forward<true>, grid, block, LEAN_LDS_BYTES, st, src, make_tabs(), pk, weff, xc_out, d_out);
-    else hipLaunchKernelGGL(k_deform_forward<false>, grid, block, LEAN_LDS_BYTES, st, src, make_tabs(), pk, weff, xc_out, d_out);
+    hipLaunchKernelGGL(KERNELS[half], grid, block, LEAN_LDS_BYTES, st, src, make_tabs(), pk, weff, xc_out, d_out);
     return hip_last("deform_forward");
 }
 
 int deform_inverse(const PointSrc& src, const float* init, const float* packed, const float* weff, int max_iters, float tol, float* y_out,
                    float* step_out, int* iters_out, hipStream_t st) {
     if (src.M <= 0) return ST_OK;
-    if (int e = deform_attrs()) return e;
+    static constexpr decltype(&k_deform_inverse<false>) KERNELS[] = {k_deform_inverse<false>, k_deform_inverse<true>};          // [HALF]
+    static DeviceOnce attr_done;
+    if (int e = allow_big_lds_once(attr_done, KERNELS, LEAN_LDS_BYTES)) return e;
     const bool half = src.M <= DEFORM_HALF_MAX_ROWS;
     const int pts = half ? 32 : 64;
     const dim3 grid((src.M + pts - 1) / pts), block(NTHREADS);
     const float4* pk = reinterpret_cast<const float4*>(packed);
-    if (half) hipLaunchKernelGGL(k_deform_inverse<true>, grid, block, LEAN_LDS_BYTES, st, src, make_tabs(), init, pk, weff, max_iters, tol, y_out,
-                                 step_out, iters_out);
-    else hipLaunchKernelGGL(k_deform_inverse<false>, grid, block, LEAN_LDS_BYTES, st, src, make_tabs(), init, pk, weff, max_iters, tol, y_out,
-                            step_out, iters_out);
+    hipLaunchKernelGGL(KERNELS[half], grid, block, LEAN_LDS_BYTES, st, src, make_tabs(), init, pk, weff, max_iters, tol, y_out, step_out,
+                       iters_out);
     return hip_last("deform_inverse");
 }
 

@@ -133,18 +133,14 @@ constexpr int JACOBIAN_HALF_MAX_POINTS = 4096;
 
 int deform_jacobian(const PointSrc& src, const float* packed, const float* weff, float* jac_out, float* xc_out, hipStream_t st) {
     if (src.M <= 0) return ST_OK;
+    static constexpr decltype(&k_deform_jacobian<false>) KERNELS[] = {k_deform_jacobian<false>, k_deform_jacobian<true>};          // [HALF]
     static DeviceOnce attr_done;
-    if (attr_done.first()) {
-        if (int e = allow_big_lds(k_deform_jacobian<false>, LEAN_LDS_BYTES)) return e;
-        if (int e = allow_big_lds(k_deform_jacobian<true>, LEAN_LDS_BYTES)) return e;
-        attr_done.done();
-    }
+    if (int e = allow_big_lds_once(attr_done, KERNELS, LEAN_LDS_BYTES)) return e;
     const bool half = src.M <= JACOBIAN_HALF_MAX_POINTS;
     const int pts = half ? 8 : 16;
     const dim3 grid((src.M + pts - 1) / pts), block(NTHREADS);
     const float4* pk = reinterpret_cast<const float4*>(packed);
-    if (half) hipLaunchKernelGGL(k_deform_jacobian<true>, grid, block, LEAN_LDS_BYTES, st, src, make_tabs(), pk, weff, jac_out, xc_out);
-    else hipLaunchKernelGGL(k_deform_jacobian<false>, grid, block, LEAN_LDS_BYTES, st, src, make_tabs(), pk, weff, jac_out, xc_out);
+    hipLaunchKernelGGL(KERNELS[half], grid, block, LEAN_LDS_BYTES, st, src, make_tabs(), pk, weff, jac_out, xc_out);
     return hip_last("deform_jacobian");
 }
 

@@ -80,4 +80,15 @@ struct DeviceOnce {
     void done() { mask[dev >> 6] |= 1ull << (dev & 63); }
 };
 
+// A launcher keeps the instantiations of its kernel in one array, indexed by the template switches: this opts every entry into big LDS
+// once per device, and the launcher then launches the one entry its arguments select.
+template <class K, int N>
+inline int allow_big_lds_once(DeviceOnce& once, K* const (&kernels)[N], int bytes) {
+    if (!once.first()) return ST_OK;
+    for (K* k : kernels)
+        if (int e = allow_big_lds(k, bytes)) return e;
+    once.done();
+    return ST_OK;
+}
+
 }  // namespace es

@@ -1,68 +1,19 @@
 // Surface tracing, no grad: where a ray meets the level set  sdf(x + D(x, t)) = tau, by the per-row rule of endosurf_amd/tracing.py
 // trace_surface (DESIGN.md 7j "Row rule") -- sphere tracing with a bracket phase -- the whole iteration of a tile's rays in ONE launch.
-// One evaluation is k_query_sdf's (query.hip), statement by statement: deform_eval (deform_eval.h) and the SDF half restated below as
-// sdf_eval, on the same 64-point tile (32 points for small batches), LDS carve, packed weights and bias prefetch.  Hence the value a
+// One evaluation is k_query_sdf's (query.hip): the two bodies that kernel is made of, deform_eval and sdf_eval (field_eval.h), on the
+// same 64-point tile (32 points for small batches), LDS carve, packed weights and bias prefetch.  Hence the value a
 // row sees is, bit for bit, what es_query_sdf_tiles returns for that point on its 32- and 64-point tiles, whatever the row's place in
 // the tile and whatever its neighbours hold.  fp32 only: decisions about signs and eps do not ride on the split kernels' budgets.
 #include <cfloat>
 
 #include "chain_common.h"
-#include "deform_eval.h"
 #include "encode.h"
+#include "field_eval.h"
 #include "host.h"
 #include "launch.h"
 #include "tabs.h"
 
 namespace es {
-
-// The SDF network on the tile's canonical rows (pxc [3][64]), output column 0 only: leaves the four k-partial sums in ``red`` (which
-// aliases the encoding rows of ``aux``) behind a barrier; row r's value is  smalln_reduce<1>(red, 0, r) + bias.  The caller puts a
-// barrier between its last read of ``red`` and the next encoding.
-template <int RTC>
-__device__ __forceinline__ void sdf_eval(float* mainT, float* aux, float* red, const float* pxc, const Tabs& tb,
-                                         const float4* __restrict__ packed, const float* __restrict__ weff, const QuadOff<RTC>& qo, int tid,
-                                         int lane, int wave) {
-    auto bias2 = [&](float(&b)[2], const float* __restrict__ bias) { b[0] = bias[64 * wave + (lane & 31)]; b[1] = bias[64 * wave + 32 + (lane & 31)]; };
-    encode3<6>(aux, 0, pxc, tid);
-    zero_rows(aux, 39, 40, tid);
-    __syncthreads();
-    float bc[2], bn[2];
-    bias2(bn, weff + tb.boff[NET_S * LAYERS + 0]);
-    {
-        f32x16 acc[RTC][2];
-        acc_zero(acc);
-        bc[0] = bn[0]; bc[1] = bn[1];
-        bias2(bn, weff + tb.boff[NET_S * LAYERS + 1]);
-        gemm_seg<5, RTC, 2>(acc, aux, packed + tb.segoff[SF0], 0, 2 * wave, lane);
-        for_quads_off(acc, qo, 0, 2 * wave, lane, [&](int row, int col, float(&v)[4], int off, int ni) {
-            add_bias4(v, bc[ni]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = softplus100(v[i]);
-            lds_store_quad_at(mainT, off, v);
-        });
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int l = 1; l <= 7; ++l) {
-        f32x16 acc[RTC][2];
-        acc_zero(acc);
-        bc[0] = bn[0]; bc[1] = bn[1];
-        if (l < 7) bias2(bn, weff + tb.boff[NET_S * LAYERS + l + 1]);
-        const int seg = l <= 4 ? SF0 + l : SF0 + l + 1;
-        gemm_seg<32, RTC, 2>(acc, mainT, packed + tb.segoff[seg], 0, 2 * wave, lane);
-        if (l == 4) gemm_seg<5, RTC, 2>(acc, aux, packed + tb.segoff[SF4A], 0, 2 * wave, lane);   // NeRF skip: + enc part
-        __syncthreads();
-        for_quads_off(acc, qo, 0, 2 * wave, lane, [&](int row, int col, float(&v)[4], int off, int ni) {
-            add_bias4(v, bc[ni]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = softplus100(v[i]);
-            lds_store_quad_at(mainT, off, v);
-        });
-        __syncthreads();
-    }
-    smalln_partial<1>(mainT, weff + tb.woff[NET_S * LAYERS + 8], 256, red, tid);
-    __syncthreads();
-}
 
 struct TraceArgs {
     const float* rays;          // [N][9]
@@ -110,17 +61,12 @@ template <bool DEFORM, bool HALF>
 __global__ __launch_bounds__(NTHREADS, 2) void k_trace_surface(TraceArgs a, Tabs tb, const float4* __restrict__ packed,
                                                             const float* __restrict__ weff) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* mainT = lds;
-    float* aux = lds + MAIN_FLOATS;
-    float* scr = aux + AUX56_FLOATS;
-    float* px = scr;          // [3][64]: the point under evaluation
-    float* pt = scr + 192;    // [64]
-    float* pxc = scr + 256;   // [3][64]: its canonical point x + D
-    float* red = aux;
+    using Tile = LeanTile<HALF>;
+    constexpr int RTC = Tile::RTC, PTS = Tile::PTS;
+    float *mainT = lds + Tile::MAIN, *aux = lds + Tile::AUX, *red = lds + Tile::RED, *px = lds + Tile::PX, *pt = lds + Tile::PT;
+    float* pxc = lds + Tile::END;          // [3][64]: the canonical point x + D of the point under evaluation (px)
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    constexpr int RTC = HALF ? 1 : 2;
-    constexpr int PTS = HALF ? 32 : 64;
     const int row0 = blockIdx.x * PTS;
     const bool mine = tid < PTS && row0 + tid < a.N;          // this thread owns a ray of the batch
     const float inf = __builtin_inff();
@@ -175,7 +121,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_trace_surface(TraceArgs a, Tabs
             const int lane_k = tid_k & 63;
             const QuadOff<RTC> qo = quad_offsets<RTC>(0, 2 * wave_k, lane_k);
             deform_eval<RTC>(mainT, aux, red, px, pt, tb, packed_k, weff_k, qo, tid_k, lane_k, wave_k);
-            if (tid_k < 192) {
+            if (tid_k < 192) {          // add_deform's statement, on the loop's own copies
                 const int i = tid_k >> 6, row = tid_k & 63;
                 pxc[i * 64 + row] = px[i * 64 + row] + (smalln_reduce<3>(red, i, row) + weff_k[b8d + i]);
             }
@@ -246,27 +192,17 @@ int trace_surface(const float* rays, int N, float tau, float eps, float relax, f
                   const float* packed, const float* weff, int use_deform, float* depth_out, int* status_out, int* iters_out,
                   float* residual_out, float* points_out, hipStream_t st) {
     if (N <= 0) return ST_OK;
+    static constexpr decltype(&k_trace_surface<true, false>) KERNELS[] = {k_trace_surface<true, false>, k_trace_surface<true, true>,          // [(DEFORM ? 0 : 2) + HALF]
+                                                                          k_trace_surface<false, false>, k_trace_surface<false, true>};
     static DeviceOnce attr_done;
-    if (attr_done.first()) {
-        if (int e = allow_big_lds(k_trace_surface<true, false>, TRACE_LDS_BYTES)) return e;
-        if (int e = allow_big_lds(k_trace_surface<true, true>, TRACE_LDS_BYTES)) return e;
-        if (int e = allow_big_lds(k_trace_surface<false, false>, TRACE_LDS_BYTES)) return e;
-        if (int e = allow_big_lds(k_trace_surface<false, true>, TRACE_LDS_BYTES)) return e;
-        attr_done.done();
-    }
+    if (int e = allow_big_lds_once(attr_done, KERNELS, TRACE_LDS_BYTES)) return e;
     const bool half = (tile_points ? tile_points : TRACE_DEFAULT_TILE) == 32;
     const int pts = half ? 32 : 64;
     const dim3 grid((N + pts - 1) / pts), block(NTHREADS);
     const float4* pk = reinterpret_cast<const float4*>(packed);
     const TraceArgs a{rays, N, max_iters, tau, eps, relax, min_step, depth_out, status_out, iters_out, residual_out, points_out};
     const Tabs tb = make_tabs();
-    if (use_deform) {
-        if (half) hipLaunchKernelGGL((k_trace_surface<true, true>), grid, block, TRACE_LDS_BYTES, st, a, tb, pk, weff);
-        else hipLaunchKernelGGL((k_trace_surface<true, false>), grid, block, TRACE_LDS_BYTES, st, a, tb, pk, weff);
-    } else {
-        if (half) hipLaunchKernelGGL((k_trace_surface<false, true>), grid, block, TRACE_LDS_BYTES, st, a, tb, pk, weff);
-        else hipLaunchKernelGGL((k_trace_surface<false, false>), grid, block, TRACE_LDS_BYTES, st, a, tb, pk, weff);
-    }
+    hipLaunchKernelGGL(KERNELS[(use_deform ? 0 : 2) + half], grid, block, TRACE_LDS_BYTES, st, a, tb, pk, weff);
     return hip_last("trace_surface");
 }
 

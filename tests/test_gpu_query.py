@@ -97,6 +97,31 @@ def test_query_sdf_tiles_choice_of_tile_height():
     assert not torch.equal(got[16], auto)                                         # (the 16-point kernel did run)
 
 
+@pytest.mark.parametrize("tile_points", [32, 64])
+def test_query_is_the_sdf_half_at_the_deformed_points(tile_points):
+    """sdf(x + D(x, t)) in one launch is, bit for bit, the query without deformation at es_deform_forward's x + D: the query, the
+    deformation kernels and the tracer are built from the same two bodies (csrc/field_eval.h), and both paths form x + D as one fp32 sum
+    of x and (D's reduction + bias).  200 rows: 7 tiles of 32 or 4 of 64, the last one ragged."""
+    lib, _lib, state, flat, weff, packed, net = _setup(11, "trained", True)
+    rng = np.random.default_rng(31)
+    M = 200
+    x = torch.from_numpy(rng.uniform(-0.8, 0.8, size=(M, 3)).astype(np.float32)).cuda()
+    t = torch.from_numpy(rng.uniform(size=(M,)).astype(np.float32)).cuda()
+    xc, d = (torch.full((M, 3), float("nan"), device="cuda") for _ in range(2))
+    pts = _lib.es_points()
+    pts.x, pts.t, pts.mode, pts.t_scalar, pts.n_per_ray, pts.ldz, pts.M = _lib.ptr(x), _lib.ptr(t), 0, 0, 1, 1, M
+    _lib.check(lib.es_deform_forward(C.byref(pts), _lib.ptr(packed), _lib.ptr(weff), _lib.ptr(xc), _lib.ptr(d), _lib.stream_ptr()), "es_deform_forward")
+    torch.cuda.synchronize()
+    fused = _query(lib, _lib, packed, weff, True, x=x, t=t, M=M, tile_points=tile_points)
+    split = _query(lib, _lib, packed, weff, False, x=xc.contiguous(), t=t, M=M, tile_points=tile_points)
+    assert bool(torch.isfinite(fused).all()) and bool((d != 0).any())
+    assert torch.equal(fused, split), float((fused - split).abs().max())
+    # xc_out - x is d_out within one ulp of the larger of |x| and |x + D|: the one rounding of the sum (as tests/test_gpu_track.py)
+    xh, xch, dh = x.cpu(), xc.cpu(), d.cpu()
+    ulp = torch.from_numpy(np.spacing(torch.maximum(xh.abs(), xch.abs()).numpy()))
+    assert bool((((xch.double() - xh.double()) - dh.double()).abs() <= ulp.double()).all())
+
+
 def test_query_sdf_ray_samples_golden():
     """Mode 1 (ray samples) against sdf values captured from the reference (coarse samples of the golden case)."""
     c = load_case("trained_deform")
