@@ -67,6 +67,8 @@ PROTOTYPES = {
     "es_deform_jacobian": (_I, [C.POINTER(es_points), _P, _P, _P, _P, _P]),
     "es_strain_rows": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "es_trace_surface": (_I, [_P, _I, _F, _F, _F, _F, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "es_sdf_hessian": (_I, [C.POINTER(es_points), _P, _P, _I, _P, _P, _P, _P]),
+    "es_curvature_rows": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "es_packed_x3_bytes": (C.c_int64, []),
     "es_pack_x3": (_I, [_P, _P, _I, _P]),
     "es_query_sdf_x3": (_I, [C.POINTER(es_points), _P, _P, _P, _I, _P, _I, _P]),

@@ -188,6 +188,25 @@ int es_trace_surface(const float* rays, int N, float tau, float eps, float relax
     return trace_surface(rays, N, tau, eps, relax, min_step, max_iters, tile_points, packed, weff, use_deform, depth_out, status_out, iters_out,
                          residual_out, points_out, (hipStream_t)stream);
 }
+int es_sdf_hessian(const es_points* pts, const float* packed, const float* weff, int tile_rows, float* sdf_out, float* grad_out,
+                   float* hess_out, void* stream) {
+    ES_REQUIRE(pts != nullptr, "es_points is null");
+    ES_REQUIRE(pts->M >= 0, "negative point count");
+    ES_REQUIRE(pts->mode == 0, "es_sdf_hessian takes explicit points (mode 0)");
+    ES_REQUIRE(tile_rows == 0 || tile_rows == 32 || tile_rows == 64, "es_sdf_hessian: tile_rows: 0 (by batch size), 32 or 64");
+    if (pts->M == 0) return ST_OK;
+    ES_REQUIRE(pts->x && packed && weff, "es_sdf_hessian: null buffer (x, packed, weff)");
+    ES_REQUIRE(sdf_out || grad_out || hess_out, "es_sdf_hessian: every output is null");
+    return sdf_hessian(pts->x, pts->M, packed, weff, tile_rows, sdf_out, grad_out, hess_out, (hipStream_t)stream);
+}
+int es_curvature_rows(const float* grad_c, const float* hess_c, const float* jac, const float* dd, int M, float* grad_o, float* hess_o,
+                      float* mean_out, float* gauss_out, float* principal_out, unsigned char* valid_out, void* stream) {
+    ES_REQUIRE(M >= 0, "negative row count");
+    if (M == 0) return ST_OK;
+    ES_REQUIRE(grad_c && hess_c, "es_curvature_rows: null buffer (grad_c, hess_c)");
+    ES_REQUIRE(grad_o || hess_o || mean_out || gauss_out || principal_out || valid_out, "es_curvature_rows: every output is null");
+    return curvature_rows(grad_c, hess_c, jac, dd, M, grad_o, hess_o, mean_out, gauss_out, principal_out, valid_out, (hipStream_t)stream);
+}
 int64_t es_packed_x3_bytes(void) { return (int64_t)packed_x3_bytes(); }
 int es_pack_x3(const float* weff, void* packed_x3, int use_deform, void* stream) {
     ES_REQUIRE(weff && packed_x3, "null buffer");

@@ -50,6 +50,12 @@ int deform_jacobian(const PointSrc& src, const float* packed, const float* weff,
 int strain_rows(const float* jac_from, const float* jac_to, const float* normals, int M, float* F_out, float* det_out, float* stretch_out,
                 float* area_out, float* surface_out, unsigned char* valid_out, hipStream_t st);
 
+// sdf_hess.hip, curvature.hip
+int sdf_hessian(const float* x, int M, const float* packed, const float* weff, int tile_rows, float* sdf_out, float* grad_out,
+                float* hess_out, hipStream_t st);
+int curvature_rows(const float* grad_c, const float* hess_c, const float* jac, const float* dd, int M, float* grad_o, float* hess_o,
+                   float* mean_out, float* gauss_out, float* principal_out, unsigned char* valid_out, hipStream_t st);
+
 // point_fwd.hip, point_bwd.hip
 int point_forward(const PointSrc& src, const float* packed, const float* weff, float* ws, int flags, int m_color, hipStream_t st,
                   const void* packed_x3 = nullptr);

@@ -11,6 +11,7 @@ import torch
 from . import _lib
 from ._device import f32, mixed_in, u8  # noqa: F401  (f32, u8: importable from here as before)
 from ._lib import check, es_composite_args, es_points, ptr, stream_ptr
+from .engine_curv import CurvMixin
 from .engine_eval import EvalMixin
 from .engine_mesh import MeshMixin
 from .engine_trace import TraceMixin
@@ -37,6 +38,7 @@ class PointCtx:
         return v
 
 
+@mixed_in(CurvMixin)
 @mixed_in(TraceMixin)
 @mixed_in(TrackMixin)
 class Engine(MeshMixin, EvalMixin):

@@ -24,6 +24,7 @@ from ._device import _on_device, mixed_in
 from .engine import Engine, f32
 from .functions import _EodLossFn, _PackFn, _PointEvalFn, _RenderFn, _SnLossFn, _SValFn
 from .model import EndoSurfNet, WNLinear, _check_arch, _reference_style_init  # noqa: F401  (the last two: importable from here as before)
+from .renderer_curv import RendererCurvMixin
 from .renderer_mesh import RendererMeshMixin
 from .renderer_trace import RendererTraceMixin
 from .renderer_track import RendererTrackMixin
@@ -31,6 +32,7 @@ from .tail import _Lazy, _LazyEodFn, _PendingEod, _Tail, _TailEvalFn
 
 
 # ---------------------------------------------------------------------------------------------------------------
+@mixed_in(RendererCurvMixin)
 @mixed_in(RendererTraceMixin)
 @mixed_in(RendererTrackMixin)
 class EndoSurfRenderer(RendererMeshMixin, nn.Module):
