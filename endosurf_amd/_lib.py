@@ -69,6 +69,8 @@ PROTOTYPES = {
     "es_trace_surface": (_I, [_P, _I, _F, _F, _F, _F, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "es_sdf_hessian": (_I, [C.POINTER(es_points), _P, _P, _I, _P, _P, _P, _P]),
     "es_curvature_rows": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "es_deform_derivatives": (_I, [C.POINTER(es_points), _P, _P, _P, _P, _P, _P, _P]),
+    "es_kinematics_rows": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "es_packed_x3_bytes": (C.c_int64, []),
     "es_pack_x3": (_I, [_P, _P, _I, _P]),
     "es_query_sdf_x3": (_I, [C.POINTER(es_points), _P, _P, _P, _I, _P, _I, _P]),

@@ -207,6 +207,27 @@ int es_curvature_rows(const float* grad_c, const float* hess_c, const float* jac
     ES_REQUIRE(grad_o || hess_o || mean_out || gauss_out || principal_out || valid_out, "es_curvature_rows: every output is null");
     return curvature_rows(grad_c, hess_c, jac, dd, M, grad_o, hess_o, mean_out, gauss_out, principal_out, valid_out, (hipStream_t)stream);
 }
+int es_deform_derivatives(const es_points* pts, const float* packed, const float* weff, float* jac_out, float* dt_out, float* dd_out,
+                          float* xc_out, void* stream) {
+    if (int e = check_deform_src(pts)) return e;
+    if (pts->M == 0) return ST_OK;
+    ES_REQUIRE(pts->x && pts->t, "mode 0 needs x and t");
+    ES_REQUIRE(packed && weff, "null buffer");
+    ES_REQUIRE(jac_out || dt_out || dd_out || xc_out, "es_deform_derivatives: every output is null");
+    return deform_derivatives(to_src(pts), packed, weff, jac_out, dt_out, dd_out, xc_out, (hipStream_t)stream);
+}
+int es_kinematics_rows(const float* jac, const float* d_t, const float* dd, const float* normals, int M, float* velocity, float* speed,
+                       float* L, float* rate, float* principal, float* divergence, float* vorticity, float* area_rate,
+                       float* surface_rates, unsigned char* valid, void* stream) {
+    ES_REQUIRE(M >= 0, "negative row count");
+    if (M == 0) return ST_OK;
+    ES_REQUIRE(jac && d_t && dd, "es_kinematics_rows: null buffer (jac, d_t, dd)");
+    ES_REQUIRE(velocity || speed || L || rate || principal || divergence || vorticity || area_rate || surface_rates || valid,
+               "es_kinematics_rows: every output is null");
+    ES_REQUIRE(normals || !(area_rate || surface_rates), "es_kinematics_rows: the surface outputs need normals");
+    return kinematics_rows(jac, d_t, dd, normals, M, velocity, speed, L, rate, principal, divergence, vorticity, area_rate, surface_rates,
+                           valid, (hipStream_t)stream);
+}
 int64_t es_packed_x3_bytes(void) { return (int64_t)packed_x3_bytes(); }
 int es_pack_x3(const float* weff, void* packed_x3, int use_deform, void* stream) {
     ES_REQUIRE(weff && packed_x3, "null buffer");

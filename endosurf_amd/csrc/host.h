@@ -56,6 +56,13 @@ int sdf_hessian(const float* x, int M, const float* packed, const float* weff, i
 int curvature_rows(const float* grad_c, const float* hess_c, const float* jac, const float* dd, int M, float* grad_o, float* hess_o,
                    float* mean_out, float* gauss_out, float* principal_out, unsigned char* valid_out, hipStream_t st);
 
+// deform_kin.hip, kinematics.hip
+int deform_derivatives(const PointSrc& src, const float* packed, const float* weff, float* jac_out, float* dt_out, float* dd_out,
+                       float* xc_out, hipStream_t st);
+int kinematics_rows(const float* jac, const float* d_t, const float* dd, const float* normals, int M, float* vel_out, float* speed_out,
+                    float* L_out, float* rate_out, float* principal_out, float* div_out, float* vort_out, float* area_out,
+                    float* surface_out, unsigned char* valid_out, hipStream_t st);
+
 // point_fwd.hip, point_bwd.hip
 int point_forward(const PointSrc& src, const float* packed, const float* weff, float* ws, int flags, int m_color, hipStream_t st,
                   const void* packed_x3 = nullptr);

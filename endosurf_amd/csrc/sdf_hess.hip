@@ -18,13 +18,12 @@
 #include "field_eval.h"
 #include "host.h"
 #include "launch.h"
+#include "row_slots.h"
 #include "tabs.h"
 
 namespace es {
 
 constexpr int HESS_ROWS = 10;          // MLP rows per point
-// the tile row of slot s of lane half hi
-__host__ __device__ constexpr int hess_row(int s, int hi) { return 32 * (s >> 4) + 8 * ((s >> 2) & 3) + 4 * hi + (s & 3); }
 
 template <bool HALF>
 __global__ __launch_bounds__(NTHREADS, 2) void k_sdf_hessian(const float* __restrict__ x, int M, Tabs tb, const float4* __restrict__ packed,
