@@ -71,6 +71,10 @@ PROTOTYPES = {
     "es_curvature_rows": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "es_deform_derivatives": (_I, [C.POINTER(es_points), _P, _P, _P, _P, _P, _P, _P]),
     "es_kinematics_rows": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "es_geodesic_seed": (_I, [_P, _P, _I, C.c_longlong, C.c_longlong, _I, _P, _P, _P, C.c_longlong, _P, _P, _P]),
+    "es_geodesic_sweep": (_I, [_P, _P, _I, C.c_longlong, C.c_longlong, _I, _P, _P, _P, _P]),
+    "es_geodesic_read": (_I, [_P, _P, _P, _I, C.c_longlong, C.c_longlong, _I, _P, _P, C.c_longlong, _P, _P, _P, _P]),
+    "es_geodesic_finish": (_I, [_P, C.c_longlong, _P, _P]),
     "es_packed_x3_bytes": (C.c_int64, []),
     "es_pack_x3": (_I, [_P, _P, _I, _P]),
     "es_query_sdf_x3": (_I, [C.POINTER(es_points), _P, _P, _P, _I, _P, _I, _P]),

@@ -60,6 +60,15 @@ static int run_backward(const es_points* pts, const float* packed, const void* p
     if (stages >> 1) return point_wgrad(pts->M, ws, flags, m_color, d_sdf, dweff, wg_scratch, (hipStream_t)stream, stages >> 1);
     return ST_OK;
 }
+// The mesh arguments every es_geodesic_* entry takes: F frames of V vertices, T triangles, S sources.
+static int check_geodesic_mesh(const float* vertices, const int* triangles, int F, long long V, long long T, int S) {
+    ES_REQUIRE(F >= 0 && V >= 0 && T >= 0, "es_geodesic: negative count (F, V, T)");
+    ES_REQUIRE(S >= 1, "es_geodesic: S must be at least 1");
+    ES_REQUIRE(V < (1ll << 31) && T < (1ll << 31), "es_geodesic: V and T must be below 2^31");
+    ES_REQUIRE(vertices || F == 0 || V == 0, "es_geodesic: null buffer (vertices)");
+    ES_REQUIRE(triangles || T == 0, "es_geodesic: null buffer (triangles)");
+    return ST_OK;
+}
 }  // namespace es
 
 using namespace es;
@@ -227,6 +236,42 @@ int es_kinematics_rows(const float* jac, const float* d_t, const float* dd, cons
     ES_REQUIRE(normals || !(area_rate || surface_rates), "es_kinematics_rows: the surface outputs need normals");
     return kinematics_rows(jac, d_t, dd, normals, M, velocity, speed, L, rate, principal, divergence, vorticity, area_rate, surface_rates,
                            valid, (hipStream_t)stream);
+}
+int es_geodesic_seed(const float* vertices, const int* triangles, int F, long long V, long long T, int S, const int* seed_field,
+                     const int* seed_vertex, const double* seed_value, long long n_seeds, unsigned long long* cur,
+                     unsigned long long* next, void* stream) {
+    if (int e = check_geodesic_mesh(vertices, triangles, F, V, T, S)) return e;
+    ES_REQUIRE(n_seeds >= 0, "es_geodesic_seed: negative count (n_seeds)");
+    if (F == 0 || V == 0) return ST_OK;
+    ES_REQUIRE(cur && next, "es_geodesic_seed: null buffer (cur, next)");
+    ES_REQUIRE(cur != next, "es_geodesic_seed: cur and next must be two buffers");
+    ES_REQUIRE(n_seeds == 0 || (seed_field && seed_vertex && seed_value), "es_geodesic_seed: null buffer (seed_field, seed_vertex, seed_value)");
+    return geodesic_seed(vertices, triangles, F, V, T, S, seed_field, seed_vertex, seed_value, n_seeds, cur, next, (hipStream_t)stream);
+}
+int es_geodesic_sweep(const float* vertices, const int* triangles, int F, long long V, long long T, int S,
+                      const unsigned long long* cur, unsigned long long* next, int* changed, void* stream) {
+    if (int e = check_geodesic_mesh(vertices, triangles, F, V, T, S)) return e;
+    ES_REQUIRE((cur && next) || F == 0 || V == 0, "es_geodesic_sweep: null buffer (cur, next)");
+    ES_REQUIRE(cur != next || !cur, "es_geodesic_sweep: cur and next must be two buffers");
+    return geodesic_sweep(vertices, triangles, F, V, T, S, cur, next, changed, (hipStream_t)stream);
+}
+int es_geodesic_read(const unsigned long long* field, const float* vertices, const int* triangles, int F, long long V, long long T, int S,
+                     const int* target_triangle, const double* target_point, long long Q, const int* source_triangle,
+                     const double* source_point, float* out, void* stream) {
+    if (int e = check_geodesic_mesh(vertices, triangles, F, V, T, S)) return e;
+    ES_REQUIRE(Q >= 0, "es_geodesic_read: negative count (Q)");
+    if (F == 0 || Q == 0) return ST_OK;
+    ES_REQUIRE(out && target_triangle && target_point, "es_geodesic_read: null buffer (target_triangle, target_point, out)");
+    ES_REQUIRE(field || V == 0, "es_geodesic_read: null buffer (field)");
+    ES_REQUIRE(!source_triangle == !source_point, "es_geodesic_read: source_triangle and source_point go together");
+    return geodesic_read(field, vertices, triangles, F, V, T, S, target_triangle, target_point, Q, source_triangle, source_point, out,
+                         (hipStream_t)stream);
+}
+int es_geodesic_finish(const unsigned long long* field, long long n, float* out, void* stream) {
+    ES_REQUIRE(n >= 0, "es_geodesic_finish: negative count (n)");
+    if (n == 0) return ST_OK;
+    ES_REQUIRE(field && out, "es_geodesic_finish: null buffer (field, out)");
+    return geodesic_finish(field, n, out, (hipStream_t)stream);
 }
 int64_t es_packed_x3_bytes(void) { return (int64_t)packed_x3_bytes(); }
 int es_pack_x3(const float* weff, void* packed_x3, int use_deform, void* stream) {

@@ -63,6 +63,17 @@ int kinematics_rows(const float* jac, const float* d_t, const float* dd, const f
                     float* L_out, float* rate_out, float* principal_out, float* div_out, float* vort_out, float* area_out,
                     float* surface_out, unsigned char* valid_out, hipStream_t st);
 
+// geodesic.hip
+int geodesic_seed(const float* vertices, const int* tris, int F, long long V, long long T, int S, const int* seed_field,
+                  const int* seed_vertex, const double* seed_value, long long n_seeds, unsigned long long* cur, unsigned long long* next,
+                  hipStream_t st);
+int geodesic_sweep(const float* vertices, const int* tris, int F, long long V, long long T, int S, const unsigned long long* cur,
+                   unsigned long long* next, int* changed, hipStream_t st);
+int geodesic_read(const unsigned long long* field, const float* vertices, const int* tris, int F, long long V, long long T, int S,
+                  const int* target_tri, const double* target_pt, long long Q, const int* source_tri, const double* source_pt, float* out,
+                  hipStream_t st);
+int geodesic_finish(const unsigned long long* field, long long n, float* out, hipStream_t st);
+
 // point_fwd.hip, point_bwd.hip
 int point_forward(const PointSrc& src, const float* packed, const float* weff, float* ws, int flags, int m_color, hipStream_t st,
                   const void* packed_x3 = nullptr);
