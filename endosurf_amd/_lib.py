@@ -75,6 +75,13 @@ PROTOTYPES = {
     "es_geodesic_sweep": (_I, [_P, _P, _I, C.c_longlong, C.c_longlong, _I, _P, _P, _P, _P]),
     "es_geodesic_read": (_I, [_P, _P, _P, _I, C.c_longlong, C.c_longlong, _I, _P, _P, C.c_longlong, _P, _P, _P, _P]),
     "es_geodesic_finish": (_I, [_P, C.c_longlong, _P, _P]),
+    "es_rigid_scratch_bytes": (C.c_int64, [_I, C.c_longlong]),
+    "es_rigid_moments": (_I, [_P, _P, _P, _I, C.c_longlong, _I, _P, _P, _P]),
+    "es_rigid_solve": (_I, [_P, _I, _P, _P, _P, _P, _P]),
+    "es_rigid_apply": (_I, [_P, _P, _P, _I, C.c_longlong, C.c_longlong, _P, _P, _P, _P, _P]),
+    "es_rigid_rmse": (_I, [_P, _I, _P, _P]),
+    "es_icp_normal_equations": (_I, [_P, _P, _P, _P, _P, _P, C.c_longlong, C.c_longlong, C.c_longlong, C.c_double, _P, _P, _P]),
+    "es_icp_update": (_I, [_P, _I, C.c_double, _P, _P]),
     "es_packed_x3_bytes": (C.c_int64, []),
     "es_pack_x3": (_I, [_P, _P, _I, _P]),
     "es_query_sdf_x3": (_I, [C.POINTER(es_points), _P, _P, _P, _I, _P, _I, _P]),

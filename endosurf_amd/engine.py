@@ -16,6 +16,7 @@ from .engine_eval import EvalMixin
 from .engine_geo import GeoMixin
 from .engine_kin import KinMixin
 from .engine_mesh import MeshMixin
+from .engine_reg import RegMixin
 from .engine_trace import TraceMixin
 from .engine_track import TrackMixin
 
@@ -40,6 +41,7 @@ class PointCtx:
         return v
 
 
+@mixed_in(RegMixin)
 @mixed_in(GeoMixin)
 @mixed_in(KinMixin)
 @mixed_in(CurvMixin)

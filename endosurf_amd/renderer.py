@@ -28,12 +28,14 @@ from .renderer_curv import RendererCurvMixin
 from .renderer_geo import RendererGeoMixin
 from .renderer_kin import RendererKinMixin
 from .renderer_mesh import RendererMeshMixin
+from .renderer_reg import RendererRegMixin
 from .renderer_trace import RendererTraceMixin
 from .renderer_track import RendererTrackMixin
 from .tail import _Lazy, _LazyEodFn, _PendingEod, _Tail, _TailEvalFn
 
 
 # ---------------------------------------------------------------------------------------------------------------
+@mixed_in(RendererRegMixin)
 @mixed_in(RendererGeoMixin)
 @mixed_in(RendererKinMixin)
 @mixed_in(RendererCurvMixin)
