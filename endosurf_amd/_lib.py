@@ -82,6 +82,12 @@ PROTOTYPES = {
     "es_rigid_rmse": (_I, [_P, _I, _P, _P]),
     "es_icp_normal_equations": (_I, [_P, _P, _P, _P, _P, _P, C.c_longlong, C.c_longlong, C.c_longlong, C.c_double, _P, _P, _P]),
     "es_icp_update": (_I, [_P, _I, C.c_double, _P, _P]),
+    "es_segment_visible": (_I, [_P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "es_pixel_rays": (_I, [_P, C.c_longlong, C.POINTER(C.c_double), _F, _P, _P]),
+    "es_flow_project": (_I, [_P, _I, C.c_longlong, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "es_flow_resolve": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, C.c_longlong, _P, _P, _P, _P, _P, _P]),
+    "es_sample_bilinear": (_I, [_P, _I, _I, _I, _I, _P, _P, C.c_longlong, C.c_longlong, _P, _P, _P]),
+    "es_flow_panel": (_I, [_P, C.c_longlong, C.c_double, _P, _P]),
     "es_packed_x3_bytes": (C.c_int64, []),
     "es_pack_x3": (_I, [_P, _P, _I, _P]),
     "es_query_sdf_x3": (_I, [C.POINTER(es_points), _P, _P, _P, _I, _P, _I, _P]),

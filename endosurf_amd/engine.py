@@ -13,6 +13,7 @@ from ._device import f32, mixed_in, u8  # noqa: F401  (f32, u8: importable from 
 from ._lib import check, es_composite_args, es_points, ptr, stream_ptr
 from .engine_curv import CurvMixin
 from .engine_eval import EvalMixin
+from .engine_flow import FlowMixin
 from .engine_geo import GeoMixin
 from .engine_kin import KinMixin
 from .engine_mesh import MeshMixin
@@ -41,6 +42,7 @@ class PointCtx:
         return v
 
 
+@mixed_in(FlowMixin)
 @mixed_in(RegMixin)
 @mixed_in(GeoMixin)
 @mixed_in(KinMixin)
