@@ -88,6 +88,9 @@ PROTOTYPES = {
     "es_flow_resolve": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, C.c_longlong, _P, _P, _P, _P, _P, _P]),
     "es_sample_bilinear": (_I, [_P, _I, _I, _I, _I, _P, _P, C.c_longlong, C.c_longlong, _P, _P, _P]),
     "es_flow_panel": (_I, [_P, C.c_longlong, C.c_double, _P, _P]),
+    "es_tsdf_integrate": (_I, [_P, C.c_longlong, _P, C.c_longlong, _I, _P, _P, _P, _P, _I, _I, C.c_double, C.c_double, _P, _P, _P, _P]),
+    "es_tsdf_finalize": (_I, [_P, _P, _P, C.c_longlong, _P, _P, _P]),
+    "es_volume_sample": (_I, [_P, _I, _I, _P, C.c_longlong, C.POINTER(C.c_double), _P, _P, _P]),
     "es_packed_x3_bytes": (C.c_int64, []),
     "es_pack_x3": (_I, [_P, _P, _I, _P]),
     "es_query_sdf_x3": (_I, [C.POINTER(es_points), _P, _P, _P, _I, _P, _I, _P]),

@@ -14,6 +14,7 @@ from ._lib import check, es_composite_args, es_points, ptr, stream_ptr
 from .engine_curv import CurvMixin
 from .engine_eval import EvalMixin
 from .engine_flow import FlowMixin
+from .engine_fuse import FuseMixin
 from .engine_geo import GeoMixin
 from .engine_kin import KinMixin
 from .engine_mesh import MeshMixin
@@ -42,6 +43,7 @@ class PointCtx:
         return v
 
 
+@mixed_in(FuseMixin)
 @mixed_in(FlowMixin)
 @mixed_in(RegMixin)
 @mixed_in(GeoMixin)

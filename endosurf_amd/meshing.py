@@ -39,20 +39,22 @@ def _tet_edges_for_case():
 _TABLE = _tet_edges_for_case()
 
 
-def marching_tetrahedra(u: np.ndarray, threshold: float = 0.0):
-    """(vertices [V,3] float in index coordinates, triangles [T,3] int) of the level set u == threshold.
+def marching_tetrahedra(u: np.ndarray, threshold: float = 0.0, return_ends: bool = False):
+    """(vertices [V,3] float in index coordinates, triangles [T,3] int[, edge_ends [V,2] int64 = the linear grid ids of each vertex's
+    inside and outside end]) of the level set u == threshold.
     'inside' = u < threshold; triangles are oriented with normals pointing to increasing u."""
     u = np.asarray(u, np.float64)
     nx, ny, nz = u.shape
+    empty = (np.zeros((0, 3), np.float64), np.zeros((0, 3), np.int64)) + ((np.zeros((0, 2), np.int64),) if return_ends else ())
     if min(nx, ny, nz) < 2:
-        return np.zeros((0, 3), np.float64), np.zeros((0, 3), np.int64)
+        return empty
     inside = u < threshold
     # cells that the level set crosses
     blk = [inside[dx:nx - 1 + dx, dy:ny - 1 + dy, dz:nz - 1 + dz] for dx, dy, dz in _CORNER]
     cnt = np.sum(blk, axis=0)
     ci, cj, ck = np.nonzero((cnt > 0) & (cnt < 8))
     if ci.size == 0:
-        return np.zeros((0, 3), np.float64), np.zeros((0, 3), np.int64)
+        return empty
     base = np.stack([ci, cj, ck], -1)                                     # [C,3]
     corner_idx = base[:, None, :] + _CORNER[None]                         # [C,8,3]
     lin = (corner_idx[..., 0] * ny + corner_idx[..., 1]) * nz + corner_idx[..., 2]     # [C,8] linear grid ids
@@ -82,7 +84,7 @@ def marching_tetrahedra(u: np.ndarray, threshold: float = 0.0):
     flip = np.einsum("ij,ij->i", n, ib - ia) < 0
     tris[flip] = tris[flip][:, [0, 2, 1]]
     keep = (tris[:, 0] != tris[:, 1]) & (tris[:, 1] != tris[:, 2]) & (tris[:, 0] != tris[:, 2])
-    return verts, tris[keep]
+    return (verts, tris[keep], np.stack([ea, eb], -1).astype(np.int64)) if return_ends else (verts, tris[keep])
 
 
 # ---- cube triangulation (numpy twin of csrc/cubes.hip; the rule is this project's own: DESIGN.md 7a "Cube triangulation") ---------------

@@ -26,6 +26,7 @@ from .functions import _EodLossFn, _PackFn, _PointEvalFn, _RenderFn, _SnLossFn, 
 from .model import EndoSurfNet, WNLinear, _check_arch, _reference_style_init  # noqa: F401  (the last two: importable from here as before)
 from .renderer_curv import RendererCurvMixin
 from .renderer_flow import RendererFlowMixin
+from .renderer_fuse import RendererFuseMixin
 from .renderer_geo import RendererGeoMixin
 from .renderer_kin import RendererKinMixin
 from .renderer_mesh import RendererMeshMixin
@@ -36,6 +37,7 @@ from .tail import _Lazy, _LazyEodFn, _PendingEod, _Tail, _TailEvalFn
 
 
 # ---------------------------------------------------------------------------------------------------------------
+@mixed_in(RendererFuseMixin)
 @mixed_in(RendererFlowMixin)
 @mixed_in(RendererRegMixin)
 @mixed_in(RendererGeoMixin)
