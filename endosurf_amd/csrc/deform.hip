@@ -117,13 +117,9 @@ int deform_forward(const PointSrc& src, const float* packed, const float* weff, 
     if (src.M <= 0) return ST_OK;
     static constexpr decltype(&k_deform_forward<false>) KERNELS[] = {k_deform_forward<false>, k_deform_forward<true>};          // [HALF]
     static DeviceOnce attr_done;
-    if (int e = allow_big_lds_once(attr_done, KERNELS, LEAN_LDS_BYTES)) return e;
     const bool half = src.M <= DEFORM_HALF_MAX_ROWS;
-    const int pts = half ? 32 : 64;
-    const dim3 grid((src.M + pts - 1) / pts), block(NTHREADS);
-    const float4* pk = reinterpret_cast<const float4*>(packed);
-    hipLaunchKernelGGL(KERNELS[half], grid, block, LEAN_LDS_BYTES, st, src, make_tabs(), pk, weff, xc_out, d_out);
-    return hip_last("deform_forward");
+    return launch_lean(KERNELS, attr_done, half, LEAN_LDS_BYTES, src.M, half ? 32 : 64, st, "deform_forward", src, make_tabs(),
+                       reinterpret_cast<const float4*>(packed), weff, xc_out, d_out);
 }
 
 int deform_inverse(const PointSrc& src, const float* init, const float* packed, const float* weff, int max_iters, float tol, float* y_out,
@@ -131,14 +127,9 @@ int deform_inverse(const PointSrc& src, const float* init, const float* packed, 
     if (src.M <= 0) return ST_OK;
     static constexpr decltype(&k_deform_inverse<false>) KERNELS[] = {k_deform_inverse<false>, k_deform_inverse<true>};          // [HALF]
     static DeviceOnce attr_done;
-    if (int e = allow_big_lds_once(attr_done, KERNELS, LEAN_LDS_BYTES)) return e;
     const bool half = src.M <= DEFORM_HALF_MAX_ROWS;
-    const int pts = half ? 32 : 64;
-    const dim3 grid((src.M + pts - 1) / pts), block(NTHREADS);
-    const float4* pk = reinterpret_cast<const float4*>(packed);
-    hipLaunchKernelGGL(KERNELS[half], grid, block, LEAN_LDS_BYTES, st, src, make_tabs(), init, pk, weff, max_iters, tol, y_out, step_out,
-                       iters_out);
-    return hip_last("deform_inverse");
+    return launch_lean(KERNELS, attr_done, half, LEAN_LDS_BYTES, src.M, half ? 32 : 64, st, "deform_inverse", src, make_tabs(), init,
+                       reinterpret_cast<const float4*>(packed), weff, max_iters, tol, y_out, step_out, iters_out);
 }
 
 }  // namespace es

@@ -5,8 +5,9 @@
 // row's D and a row's sdf have the same bits in all of them, whatever the row's place in the tile and whatever its neighbours hold:
 // the tests that compare them bit for bit confirm a property this file gives by construction.  (k_deform_forward's load stage and the
 // tracer's x + D stay written out in their kernels: through LeanTile::load_points / add_deform the compiler orders a few prologue
-// instructions differently, and the ISA of those two units is held fixed.  k_deform_jacobian, deform_jac.hip, has its own body: four
-// rows per point and a gating epilogue.)
+// instructions differently, and the ISA of those two units is held fixed.  The forward-mode kernels, k_deform_jet of deform_jet.hip and
+// k_sdf_hessian of sdf_hess.hip, have bodies of their own -- several rows per point and an epilogue that gates or differentiates --
+// and what they share is in jet.h.)
 #pragma once
 #include "chain_common.h"
 #include "encode.h"

@@ -45,7 +45,7 @@ int trace_surface(const float* rays, int N, float tau, float eps, float relax, f
                   const float* packed, const float* weff, int use_deform, float* depth_out, int* status_out, int* iters_out,
                   float* residual_out, float* points_out, hipStream_t st);
 
-// deform_jac.hip, strain.hip
+// deform_jet.hip, strain.hip
 int deform_jacobian(const PointSrc& src, const float* packed, const float* weff, float* jac_out, float* xc_out, hipStream_t st);
 int strain_rows(const float* jac_from, const float* jac_to, const float* normals, int M, float* F_out, float* det_out, float* stretch_out,
                 float* area_out, float* surface_out, unsigned char* valid_out, hipStream_t st);
@@ -56,7 +56,7 @@ int sdf_hessian(const float* x, int M, const float* packed, const float* weff, i
 int curvature_rows(const float* grad_c, const float* hess_c, const float* jac, const float* dd, int M, float* grad_o, float* hess_o,
                    float* mean_out, float* gauss_out, float* principal_out, unsigned char* valid_out, hipStream_t st);
 
-// deform_kin.hip, kinematics.hip
+// deform_jet.hip, kinematics.hip
 int deform_derivatives(const PointSrc& src, const float* packed, const float* weff, float* jac_out, float* dt_out, float* dd_out,
                        float* xc_out, hipStream_t st);
 int kinematics_rows(const float* jac, const float* d_t, const float* dd, const float* normals, int M, float* vel_out, float* speed_out,

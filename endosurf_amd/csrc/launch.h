@@ -91,4 +91,15 @@ inline int allow_big_lds_once(DeviceOnce& once, K* const (&kernels)[N], int byte
     return ST_OK;
 }
 
+// The launch of a lean-tile kernel (one workgroup of 256 threads per tile of ``pts`` points, ``lds_bytes`` of dynamic LDS), written
+// once: every entry of ``kernels`` is opted into big LDS once per device, then entry ``which`` runs on ceil(rows / pts) workgroups.
+template <class K, int N, class... Args>
+inline int launch_lean(K* const (&kernels)[N], DeviceOnce& once, int which, int lds_bytes, long long rows, int pts, hipStream_t st,
+                       const char* name, const Args&... args) {
+    if (int e = allow_big_lds_once(once, kernels, lds_bytes)) return e;
+    const dim3 grid((unsigned)((rows + pts - 1) / pts)), block(256);
+    hipLaunchKernelGGL(kernels[which], grid, block, lds_bytes, st, args...);
+    return hip_last(name);
+}
+
 }  // namespace es

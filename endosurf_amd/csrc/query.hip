@@ -64,16 +64,13 @@ int query_sdf(const PointSrc& src, const float* packed, const float* weff, float
     static constexpr decltype(&k_query_sdf<true, false>) KERNELS[] = {k_query_sdf<true, false>, k_query_sdf<true, true>,          // [(DEFORM ? 0 : 2) + HALF]
                                                                       k_query_sdf<false, false>, k_query_sdf<false, true>};
     static DeviceOnce attr_done;
-    if (int e = allow_big_lds_once(attr_done, KERNELS, LEAN_LDS_BYTES)) return e;
+    if (int e = allow_big_lds_once(attr_done, KERNELS, LEAN_LDS_BYTES)) return e;          // (here already: before the empty batch's return)
     if (src.M <= 0) return ST_OK;
     const Tabs tb = make_tabs();
     const bool half = tp == 32;
-    const int pts = half ? 32 : 64;
-    const dim3 grid((src.M + pts - 1) / pts), block(NTHREADS);
-    const float4* pk = reinterpret_cast<const float4*>(packed);
     ScopedTimer tm(ray_done ? KID_QUERY_EXIT : KID_QUERY, src.M, st);     // launches with early-exit tiles are not counted as work
-    hipLaunchKernelGGL(KERNELS[(use_deform ? 0 : 2) + half], grid, block, LEAN_LDS_BYTES, st, src, tb, pk, weff, sdf_out, ld_out, ray_done);
-    return hip_last("query_sdf");
+    return launch_lean(KERNELS, attr_done, (use_deform ? 0 : 2) + half, LEAN_LDS_BYTES, src.M, half ? 32 : 64, st, "query_sdf", src, tb,
+                       reinterpret_cast<const float4*>(packed), weff, sdf_out, ld_out, ray_done);
 }
 
 }  // namespace es

@@ -7,18 +7,16 @@
 // (field_eval.h), so the value row's sums are taken in that order: a point's value is, bit for bit, es_query_sdf_tiles' without
 // deformation on its 32- and 64-point tiles, whatever the row's place in the tile and whatever its neighbours hold.
 //
-// Row layout.  The MFMA result has col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5): a lane half owns 16 rows of each
-// 32-row tile, as four quads.  Those rows, across the tile's row tiles, are the half's SLOTS (32 on the 64-row tile, 16 on the HALF
-// tile: slot = 16 ri + reg), and point p of a half takes slots 10 p .. 10 p + 9: three points per half, six per 64-row tile (60 of 64
-// rows), one per half and two per 32-row tile (20 of 32).  Every product of a point's rows is then between registers of one lane, the
-// epilogue stays in registers, and a quad is still four consecutive rows (lds_store_quad_at as it is).  Unused slots carry zeros.
+// Row layout (jet.h): point q of a lane half takes slots 10 q .. 10 q + 9: three points per half, six per 64-row tile (60 of 64 rows),
+// one per half and two per 32-row tile (20 of 32).  Every product of a point's rows is then between registers of one lane and the
+// epilogue stays in registers.  Unused slots carry zeros.
 // fp32 only, explicit points only; the time is not read.
 #include "chain_common.h"
 #include "encode.h"
 #include "field_eval.h"
 #include "host.h"
+#include "jet.h"
 #include "launch.h"
-#include "row_slots.h"
 #include "tabs.h"
 
 namespace es {
@@ -32,8 +30,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sdf_hessian(const float* __rest
     extern __shared__ __attribute__((aligned(16))) float lds[];
     using Tile = LeanTile<HALF>;
     constexpr int RTC = Tile::RTC;
-    constexpr int PPH = 16 * RTC / HESS_ROWS;          // points per lane half: 3, or 1 on the HALF tile
-    constexpr int PTS = 2 * PPH;
+    constexpr int PPH = jet_pph(HESS_ROWS, RTC), PTS = jet_pts(HESS_ROWS, RTC);          // points per lane half: 3, or 1 on the HALF tile
     float *mainT = lds + Tile::MAIN, *aux = lds + Tile::AUX, *red = lds + Tile::RED, *px = lds + Tile::PX;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -50,31 +47,15 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sdf_hessian(const float* __rest
         const int p = tid & 7, item = tid >> 3;
         if (p < PTS && item < 19) {
             const int hi = p / PPH, s0 = HESS_ROWS * (p % PPH);
-            const int r0 = hess_row(s0, hi);
-            if (item < 18) {
-                const int c = item % 3, i = item / 3;
-                const int r1 = hess_row(s0 + 1 + c, hi), r2 = hess_row(s0 + (c == 0 ? 4 : (c == 1 ? 7 : 9)), hi);
-                const float f = (float)(1 << i);
-                float s, co;
-                sincosf(px[c * 64 + p] * f, &s, &co);
-                const int ks = enc_index(3, i, 0, c), kc = enc_index(3, i, 1, c);
-                aux[swz(ks, r0)] = s;
-                aux[swz(kc, r0)] = co;
-                aux[swz(ks, r1)] = f * co;
-                aux[swz(kc, r1)] = -f * s;
-                aux[swz(ks, r2)] = -(f * f) * s;
-                aux[swz(kc, r2)] = -(f * f) * co;
-            } else {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) { aux[swz(c, r0)] = px[c * 64 + p]; aux[swz(c, hess_row(s0 + 1 + c, hi))] = 1.f; }
-            }
+            jet_encode3<6>(aux, item, px, p, jet_row(s0, hi), [&](int c) { return jet_row(s0 + 1 + c, hi); },
+                           [&](int c) { return jet_row(s0 + (c == 0 ? 4 : (c == 1 ? 7 : 9)), hi); });
         }
     }
     __syncthreads();
 
     const QuadOff<RTC> qo = quad_offsets<RTC>(0, 2 * wave, lane);
     auto bias2 = [&](float(&b)[2], const float* __restrict__ bias) { b[0] = bias[64 * wave + (lane & 31)]; b[1] = bias[64 * wave + 32 + (lane & 31)]; };
-    // the second-order activation, in registers: slot s of n-tile ni is acc[s >> 4][ni][s & 15]
+    // the second-order activation, in registers
     auto epi = [&](f32x16(&acc)[RTC][2], const float(&bc)[2]) {
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) {
@@ -82,7 +63,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sdf_hessian(const float* __rest
             for (int p = 0; p < PPH; ++p) {
                 float z[HESS_ROWS];
 #pragma unroll
-                for (int c = 0; c < HESS_ROWS; ++c) z[c] = acc[(HESS_ROWS * p + c) >> 4][ni][(HESS_ROWS * p + c) & 15];
+                for (int c = 0; c < HESS_ROWS; ++c) z[c] = jet_get(acc, ni, HESS_ROWS * p + c);
                 const float s = softplus100(z[0] + bc[ni]);
                 const float d1 = softplus100_grad_from_s(s);
                 const float d2 = 100.f * d1 * __expf(-100.f * s);
@@ -96,7 +77,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sdf_hessian(const float* __rest
 #pragma unroll
                     for (int k = j; k < 3; ++k, ++c) h[c] = fmaf(d2 * z[1 + j], z[1 + k], d1 * z[c]);
 #pragma unroll
-                for (int cc = 0; cc < HESS_ROWS; ++cc) acc[(HESS_ROWS * p + cc) >> 4][ni][(HESS_ROWS * p + cc) & 15] = h[cc];
+                for (int cc = 0; cc < HESS_ROWS; ++cc) jet_set(acc, ni, HESS_ROWS * p + cc, h[cc]);
             }
         }
         for_quads_off(acc, qo, 0, 2 * wave, lane, [&](int row, int col, float(&v)[4], int off, int ni) { lds_store_quad_at(mainT, off, v); });
@@ -128,7 +109,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sdf_hessian(const float* __rest
     smalln_partial<1>(mainT, weff + tb.woff[NET_S * LAYERS + 8], 256, red, tid);          // the last layer is linear: one row in, one row out
     __syncthreads();
     if (tid < 64) {
-        const int row = tid, hi = (row >> 2) & 1, slot = 16 * (row >> 5) + 4 * ((row >> 3) & 3) + (row & 3);
+        const int row = tid, hi = (row >> 2) & 1, slot = jet_slot(row);
         const int q = slot / HESS_ROWS, c = slot - HESS_ROWS * q;
         if (q < PPH && pt0 + hi * PPH + q < M) {
             const size_t gp = (size_t)(pt0 + hi * PPH + q);
@@ -146,7 +127,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_sdf_hessian(const float* __rest
     }
 }
 
-// The 32-row tile up to this many points, the 64-row tile above.  The family's threshold of 16 384 MLP rows (deform.hip, deform_jac.hip)
+// The 32-row tile up to this many points, the 64-row tile above.  The family's threshold of 16 384 MLP rows (deform.hip, deform_jet.hip)
 // would be 1 638 points at ten rows per point; it is lower here because the short tile carries points on 20 of its 32 rows where the
 // tall one has 60 of 64.  Measured, 32- against 64-row tiles: 0.090 against 0.144 ms at 512 points (256 short tiles, one
 // per CU), 0.141 against 0.142 at 1 024, 0.205 against 0.144 at 1 280, 0.207 against 0.145 at 1 536.
@@ -157,13 +138,9 @@ int sdf_hessian(const float* x, int M, const float* packed, const float* weff, i
     if (M <= 0) return ST_OK;
     static constexpr decltype(&k_sdf_hessian<false>) KERNELS[] = {k_sdf_hessian<false>, k_sdf_hessian<true>};          // [HALF]
     static DeviceOnce attr_done;
-    if (int e = allow_big_lds_once(attr_done, KERNELS, LEAN_LDS_BYTES)) return e;
     const bool half = tile_rows ? tile_rows == 32 : M <= HESSIAN_HALF_MAX_POINTS;
-    const int pts = half ? 2 : 6;
-    const dim3 grid((M + pts - 1) / pts), block(NTHREADS);
-    const float4* pk = reinterpret_cast<const float4*>(packed);
-    hipLaunchKernelGGL(KERNELS[half], grid, block, LEAN_LDS_BYTES, st, x, M, make_tabs(), pk, weff, sdf_out, grad_out, hess_out);
-    return hip_last("sdf_hessian");
+    return launch_lean(KERNELS, attr_done, half, LEAN_LDS_BYTES, M, jet_pts(HESS_ROWS, half ? 1 : 2), st, "sdf_hessian", x, M, make_tabs(),
+                       reinterpret_cast<const float4*>(packed), weff, sdf_out, grad_out, hess_out);
 }
 
 }  // namespace es

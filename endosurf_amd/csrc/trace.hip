@@ -195,15 +195,10 @@ int trace_surface(const float* rays, int N, float tau, float eps, float relax, f
     static constexpr decltype(&k_trace_surface<true, false>) KERNELS[] = {k_trace_surface<true, false>, k_trace_surface<true, true>,          // [(DEFORM ? 0 : 2) + HALF]
                                                                           k_trace_surface<false, false>, k_trace_surface<false, true>};
     static DeviceOnce attr_done;
-    if (int e = allow_big_lds_once(attr_done, KERNELS, TRACE_LDS_BYTES)) return e;
     const bool half = (tile_points ? tile_points : TRACE_DEFAULT_TILE) == 32;
-    const int pts = half ? 32 : 64;
-    const dim3 grid((N + pts - 1) / pts), block(NTHREADS);
-    const float4* pk = reinterpret_cast<const float4*>(packed);
     const TraceArgs a{rays, N, max_iters, tau, eps, relax, min_step, depth_out, status_out, iters_out, residual_out, points_out};
-    const Tabs tb = make_tabs();
-    hipLaunchKernelGGL(KERNELS[(use_deform ? 0 : 2) + half], grid, block, TRACE_LDS_BYTES, st, a, tb, pk, weff);
-    return hip_last("trace_surface");
+    return launch_lean(KERNELS, attr_done, (use_deform ? 0 : 2) + half, TRACE_LDS_BYTES, N, half ? 32 : 64, st, "trace_surface", a,
+                       make_tabs(), reinterpret_cast<const float4*>(packed), weff);
 }
 
 }  // namespace es

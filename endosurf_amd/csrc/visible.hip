@@ -170,13 +170,9 @@ static int segment_visible(const VisibleArgs& a, int tile_points, const float* p
     static constexpr decltype(&k_segment_visible<true, false>) KERNELS[] = {k_segment_visible<true, false>, k_segment_visible<true, true>,          // [(DEFORM ? 0 : 2) + HALF]
                                                                             k_segment_visible<false, false>, k_segment_visible<false, true>};
     static DeviceOnce attr_done;
-    if (int e = allow_big_lds_once(attr_done, KERNELS, VIS_LDS_BYTES)) return e;
     const bool half = (tile_points ? tile_points : VIS_DEFAULT_TILE) == 32;
-    const int pts = half ? 32 : 64;
-    const dim3 grid((unsigned)(((long long)a.M + pts - 1) / pts)), block(NTHREADS);
-    const Tabs tb = make_tabs();
-    hipLaunchKernelGGL(KERNELS[(use_deform ? 0 : 2) + half], grid, block, VIS_LDS_BYTES, st, a, tb, reinterpret_cast<const float4*>(packed), weff);
-    return hip_last("es_segment_visible");
+    return launch_lean(KERNELS, attr_done, (use_deform ? 0 : 2) + half, VIS_LDS_BYTES, a.M, half ? 32 : 64, st, "es_segment_visible", a,
+                       make_tabs(), reinterpret_cast<const float4*>(packed), weff);
 }
 
 }  // namespace es

@@ -1,5 +1,5 @@
 """The kinematics methods of ``engine.Engine`` (a mixin): the Jacobian, the time derivative and the pure second derivatives of the
-deformation map in one launch, csrc/deform_kin.hip, and the velocity and strain rate row by row, csrc/kinematics.hip."""
+deformation map in one launch, csrc/deform_jet.hip, and the velocity and strain rate row by row, csrc/kinematics.hip."""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,7 +14,7 @@ class KinMixin:
     def deform_derivatives(self, pts: es_points, weff, packed, want_xc: bool = False):
         """dict(jac [M,3,3] = I + dD/dx, d_t [M,3] = dD/dt, dd [M,3,3] with dd[m,i,k] = d2 D_i / d x_k^2 and, with ``want_xc``, xc [M,3] =
         x + D) for explicit points: the value, the three spatial tangents, the time tangent and the three pure second tangents in one
-        launch of the deformation network alone (csrc/deform_kin.hip), nothing saved, fp32 whatever ``split_precision`` says; ``jac``
+        launch of the deformation network alone (csrc/deform_jet.hip), nothing saved, fp32 whatever ``split_precision`` says; ``jac``
         and ``xc`` are ``deform_jacobian``'s bit for bit.  No read-back, no synchronisation."""
         out = {"jac": self.empty(pts.M, 3, 3), "d_t": self.empty(pts.M, 3), "dd": self.empty(pts.M, 3, 3)}
         if want_xc:

@@ -1,5 +1,5 @@
 """The deformation-only methods of ``engine.Engine`` (a mixin): D(x, t) and the inverse of x -> x + D(x, t), csrc/deform.hip; the
-Jacobian of that map in one launch, csrc/deform_jac.hip, and the strain of the tracked map row by row, csrc/strain.hip."""
+Jacobian of that map in one launch, csrc/deform_jet.hip, and the strain of the tracked map row by row, csrc/strain.hip."""
 from __future__ import annotations
 
 import ctypes as C
@@ -38,7 +38,7 @@ class TrackMixin:
 
     def deform_jacobian(self, pts: es_points, weff, packed, want_xc: bool = False):
         """J(x, t) = I + dD/dx [M,3,3] (dim_out, dim_in) for explicit points, with ``want_xc`` the pair (J, x_c = x + D [M,3]): the
-        value and the three forward tangents in one launch of the deformation network alone (csrc/deform_jac.hip), nothing saved, fp32
+        value and the three forward tangents in one launch of the deformation network alone (csrc/deform_jet.hip), nothing saved, fp32
         whatever ``split_precision`` says.  No read-back, no synchronisation."""
         jac = self.empty(pts.M, 3, 3)
         xc = self.empty(pts.M, 3) if want_xc else None

@@ -23,7 +23,7 @@ Plain torch / numpy; results come back in the dtype and on the device of the inp
 dd [M,3,3] or [M,3,3,3][, d_xt [M,3,3]])`` is any callable on [M,3] points and [M] times, e.g. autograd through the fp64 oracle.
 ``kinematics_rows`` is the written specification and the fp64 twin of the device kernel (csrc/kinematics.hip): the
 functions that compose it take ``rows_fn=``, a callable ``(jac, d_t, dd, normals) -> dict`` that replaces it, and the renderer's methods
-of the same names (``renderer_kin``) pass the kernel there with the model's own derivatives (csrc/deform_kin.hip) as ``derivs_fn``.
+of the same names (``renderer_kin``) pass the kernel there with the model's own derivatives (csrc/deform_jet.hip) as ``derivs_fn``.
 
 Validity (the rule of ``strain``): a row is valid exactly when det J > 0 -- the map preserves orientation there, the
 condition under which it is locally invertible and v means anything --, every entry of its inputs is finite and, where normals are

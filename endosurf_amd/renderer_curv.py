@@ -1,6 +1,6 @@
 """Surface curvature of ``renderer.EndoSurfRenderer`` (a mixin): ``curvature``'s functions with the model's own networks under them --
 value, gradient and Hessian of the SDF network in one launch (csrc/sdf_hess.hip), composed with the deformation's Jacobian
-(csrc/deform_jac.hip) and the curvature of its encodings (the fp32 point forward's ``ES_WS_CURV``) row by row (csrc/curvature.hip,
+(csrc/deform_jet.hip) and the curvature of its encodings (the fp32 point forward's ``ES_WS_CURV``) row by row (csrc/curvature.hip,
 DESIGN.md 7k)."""
 from __future__ import annotations
 

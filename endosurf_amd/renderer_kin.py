@@ -1,5 +1,5 @@
 """Tissue velocity and strain rate of ``renderer.EndoSurfRenderer`` (a mixin): ``kinematics``' functions with the model's own
-deformation network under them -- J, dD/dt and the pure second derivatives of D in one launch (csrc/deform_kin.hip), the per-row
+deformation network under them -- J, dD/dt and the pure second derivatives of D in one launch (csrc/deform_jet.hip), the per-row
 algebra in another (csrc/kinematics.hip)."""
 from __future__ import annotations
 
@@ -13,7 +13,7 @@ class RendererKinMixin:
     @_on_device
     def deform_derivatives(self, pts, t):
         """dict(jac [M,3,3] = I + dD/dx, d_t [M,3] = dD/dt, dd [M,3,3] with dd[m,i,k] = d2 D_i / d x_k^2) for [M,3] points and [M] / scalar
-        time, no grad: ``kinematics``' ``derivs_fn``, one launch (csrc/deform_kin.hip).  Without a deformation network J = I, D_t = 0,
+        time, no grad: ``kinematics``' ``derivs_fn``, one launch (csrc/deform_jet.hip).  Without a deformation network J = I, D_t = 0,
         dd = 0, and no launch."""
         x = self._track_rows(pts)
         M = x.shape[0]

@@ -1,6 +1,6 @@
 """The surface tracks of ``renderer.EndoSurfRenderer`` (a mixin): ``tracking``'s functions with the model's own deformation network
 under them -- D(x, t) in one launch of the deformation network alone, the inverse as one launch per solve (csrc/deform.hip) -- and
-``strain``'s functions likewise: the Jacobian of the deformation in one launch (csrc/deform_jac.hip), the per-row algebra in another
+``strain``'s functions likewise: the Jacobian of the deformation in one launch (csrc/deform_jet.hip), the per-row algebra in another
 (csrc/strain.hip)."""
 from __future__ import annotations
 
@@ -118,7 +118,7 @@ class RendererTrackMixin:
     @_on_device
     def deform_jacobian(self, pts, t):
         """J(x, t) = I + dD/dx [M,3,3] (dim_out, dim_in) for [M,3] points and [M] / scalar time, no grad: ``strain``'s ``jacobian_fn``,
-        one launch (csrc/deform_jac.hip).  Identities, and no launch, without a deformation network."""
+        one launch (csrc/deform_jet.hip).  Identities, and no launch, without a deformation network."""
         x = self._track_rows(pts)
         M = x.shape[0]
         tt = self._track_times(t, M)

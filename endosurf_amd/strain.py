@@ -14,7 +14,7 @@ Plain torch / numpy; results come back in the dtype and on the device of the inp
 on [M,3] points and [M] times, e.g. the fp64 oracle's ``lambda y, t: net.deform(y, t)[1]``.  ``strain_rows`` is the written specification
 and the fp64 twin of the device kernel (csrc/strain.hip): the functions that compose it take ``rows_fn=``, a callable
 ``(jac_from, jac_to, normals) -> dict`` that replaces it, and the renderer's methods of the same names (``renderer_track``) pass the
-kernel there with the model's own Jacobian (csrc/deform_jac.hip) as ``jacobian_fn``.
+kernel there with the model's own Jacobian (csrc/deform_jet.hip) as ``jacobian_fn``.
 
 Validity: a row is valid exactly when det J_from > 0 and det J_to > 0 -- both maps preserve orientation there, the
 condition under which psi_t is locally invertible and F means anything -- and, where normals are given, its normal has a finite positive

@@ -1,4 +1,4 @@
-"""GPU: tissue velocity and strain rate.  Kernel level through the C ABI -- es_deform_derivatives (csrc/deform_kin.hip)
+"""GPU: tissue velocity and strain rate.  Kernel level through the C ABI -- es_deform_derivatives (csrc/deform_jet.hip)
 bit for bit against es_deform_jacobian and against the fp64 reference of ``kinematics_ref`` on rows screened away from the ReLU kinks,
 es_kinematics_rows (csrc/kinematics.hip) against the fp64 numpy twin ``kinematics.kinematics_rows`` -- then Engine and renderer.
 Every test prints the figures it asserts on."""
@@ -21,7 +21,7 @@ from endosurf_amd import kinematics, tracking
 pytestmark = pytest.mark.gpu
 
 M = 200
-HALF_MAX_POINTS = 3072          # 4-point (32-row) tiles up to here, 8-point (64-row) tiles above (csrc/deform_kin.hip)
+HALF_MAX_POINTS = 3072          # 4-point (32-row) tiles up to here, 8-point (64-row) tiles above (csrc/deform_jet.hip)
 MARGIN = 4.0                    # x the worst-row error of the oracle's own fp32 run: the yardstick of 7i's end-to-end test
 RTOL, ATOL = 2.4e-7, 1e-13      # two fp32 ulps: the kernel's fp64 error is far below half an ulp, only the final rounding can differ
 OUTS = ("jac", "d_t", "dd", "xc")

@@ -1,4 +1,4 @@
-"""GPU: tissue strain along surface tracks.  Kernel level through the C ABI -- es_deform_jacobian (csrc/deform_jac.hip)
+"""GPU: tissue strain along surface tracks.  Kernel level through the C ABI -- es_deform_jacobian (csrc/deform_jet.hip)
 against the fp64 oracle's closed-form Jacobian on rows screened away from the ReLU kinks, es_strain_rows (csrc/strain.hip) against the
 fp64 numpy twin ``strain.strain_rows`` -- then Engine and renderer.  Every test prints the figures it asserts on."""
 import ctypes as C
@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 CASES = [(11, "trained"), (23, "trained"), (21, "init")]
 M = 200
-HALF_MAX_POINTS = 4096          # 8-point tiles up to here, 16-point tiles above (csrc/deform_jac.hip)
+HALF_MAX_POINTS = 4096          # 8-point tiles up to here, 16-point tiles above (csrc/deform_jet.hip)
 RTOL, ATOL = 2.4e-7, 1e-13      # two fp32 ulps: the kernel's fp64 error is far below half an ulp, only the final rounding can differ
 KEYS = ("F", "det", "stretch", "area", "surface_stretch", "valid")
 

@@ -1,15 +1,15 @@
 #!/usr/bin/env python3
-"""Time the kinematics kernels on the GPU box (csrc/deform_kin.hip, csrc/kinematics.hip) on the seed-11 ``trained`` weights:
+"""Time the kinematics kernels on the GPU box (csrc/deform_jet.hip, csrc/kinematics.hip) on the seed-11 ``trained`` weights:
 es_deform_derivatives -- value, three tangents, the time tangent and three second tangents of every point in one launch, 8 MLP rows per
-point -- against es_deform_jacobian on the same points (4 rows per point: about half the time is the expectation; that kernel is the
-parent commit's, this change does not touch it) at M = 2 630, 4 096, 65 536 and 1 048 576 points (uniform in [-0.8, 0.8]^3, a random
+point -- against es_deform_jacobian on the same points (4 rows per point, the four-row instance of the same kernel: about half the
+time is the expectation) at M = 2 630, 4 096, 65 536 and 1 048 576 points (uniform in [-0.8, 0.8]^3, a random
 time per row), and around the tile-height threshold; the finite-difference route it replaces, two ``track_points`` solves to t +- h
 from a shared time; es_kinematics_rows with and without normals at the same sizes; and ``renderer.mesh_kinematics`` on the 2 630-vertex
 mesh of DESIGN.md 7h (24^3 lattice at t = 0.3) tracked through t, t + 0.01, t + 0.02, 0.9.  Events on the launch stream, one warm-up
 each, the candidates interleaved repetition by repetition, median of 5.  Numbers are recorded, not gated.
 
 ``--tile-libs SHORT TALL``: two more builds of the library that differ from the product in one constant, KINEMATICS_HALF_MAX_POINTS of
-csrc/deform_kin.hip (INT_MAX: always the 32-row tile; 0: always the 64-row tile).  With them the tool times both tile heights at the
+csrc/deform_jet.hip (INT_MAX: always the 32-row tile; 0: always the 64-row tile).  With them the tool times both tile heights at the
 same point counts, interleaved, which is the table the constant is chosen from.
 
     python tools/time_kinematics.py [--points 2630 4096 65536 1048576] [--tile-libs short.so tall.so] [--out profiles/kinematics_time.json]

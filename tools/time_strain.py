@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the strain kernels on the GPU box (csrc/deform_jac.hip, csrc/strain.hip) on the seed-11 ``trained`` weights: es_deform_jacobian
+"""Time the strain kernels on the GPU box (csrc/deform_jet.hip, csrc/strain.hip) on the seed-11 ``trained`` weights: es_deform_jacobian
 -- the value and the three forward tangents of every point in one launch, 4 MLP rows per point -- against the route there was before,
 ``model.get_deform_grad_from_observed_space``: three launches of the point forward chain, one per unit direction, 6 rows per point
 plus the mask and u_l workspace streams, on the same rows (points uniform in [-0.8, 0.8]^3, a random time per row) at M = 2 630,
