@@ -91,6 +91,13 @@ PROTOTYPES = {
     "es_tsdf_integrate": (_I, [_P, C.c_longlong, _P, C.c_longlong, _I, _P, _P, _P, _P, _I, _I, C.c_double, C.c_double, _P, _P, _P, _P]),
     "es_tsdf_finalize": (_I, [_P, _P, _P, C.c_longlong, _P, _P, _P]),
     "es_volume_sample": (_I, [_P, _I, _I, _P, C.c_longlong, C.POINTER(C.c_double), _P, _P, _P]),
+    "es_stereo_scratch_bytes": (C.c_int64, [_I, _I, _I]),
+    "es_stereo_census": (_I, [_P, _I, _I, _I, _P, _P]),
+    "es_sgm_cost": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "es_sgm_aggregate": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "es_sgm_select": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "es_speckle_label": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "es_speckle_apply": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "es_packed_x3_bytes": (C.c_int64, []),
     "es_pack_x3": (_I, [_P, _P, _I, _P]),
     "es_query_sdf_x3": (_I, [C.POINTER(es_points), _P, _P, _P, _I, _P, _I, _P]),

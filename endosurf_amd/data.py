@@ -115,6 +115,42 @@ class FrameSet:
         fs.scale_mat, fs.depth_scale, fs.bbox_minmax = norm["scale_mat"], scale, norm["bbox_minmax"]
         return fs
 
+    _STEREO_ARGS = ("max_disparity", "near", "far", "close", "engine", "poll")
+
+    @classmethod
+    def from_stereo(cls, colors_left, colors_right, intrinsics, poses, baseline, bounds=None, **args):
+        """The ``FrameSet`` of a rectified stereo sequence: ``colors_left`` / ``colors_right`` [n,h,w,3] (uint8, or float in [0,1]),
+        ``intrinsics`` and camera-to-world ``poses`` [n,4,4] of the left camera, ``baseline`` in the unit the depths shall have.
+        ``stereo_depth`` runs per frame with the focal length ``intrinsics[i,0,0]`` (on the device for device tensors, through the numpy
+        twin for host arrays); then ``from_raw`` with the left colours (uint8 colours divided by 255), these depths, ``color_masks`` =
+        the closed masks and ``depth_masks`` = depth > 0 unless the caller passes its own.  ``bounds`` [n,2] default to the smallest and
+        largest non-zero depth of each frame; a frame without a valid pixel raises ValueError.  Keywords: ``max_disparity`` (required),
+        ``near``, ``far``, ``close``, ``engine``, ``poll`` and the matcher's (``stereo.MATCHER_ARGS``) go to ``stereo_depth``, the rest
+        to ``from_raw``.  ``scale_mat``, ``depth_scale`` and ``bbox_minmax`` are attributes as after ``from_raw``."""
+        from .stereo import MATCHER_ARGS
+        matcher = {k: args.pop(k) for k in cls._STEREO_ARGS + MATCHER_ARGS if k in args}
+        if "max_disparity" not in matcher:
+            raise TypeError("from_stereo needs max_disparity")
+        n = int(colors_left.shape[0])
+        focal = torch.as_tensor(np.asarray(intrinsics) if not torch.is_tensor(intrinsics) else intrinsics)[:, 0, 0].double().cpu().tolist()
+        depths, closed, found = [], [], []
+        for i in range(n):
+            r = stereo_depth(colors_left[i], colors_right[i], focal[i], baseline, **matcher)
+            d = r["depth"]
+            if not bool(r["depth_mask"].any()):
+                raise ValueError(f"from_stereo: frame {i} has no valid pixel")
+            seen = d[r["depth_mask"]]
+            found.append(torch.stack([seen.min(), seen.max()]))
+            depths.append(d)
+            closed.append(r["color_mask"])
+        depths, closed = torch.stack(depths), torch.stack(closed).to(torch.float32)
+        bounds = torch.stack(found) if bounds is None else bounds
+        args.setdefault("depth_masks", (depths > 0).to(torch.float32)[..., None])
+        colors = colors_left if torch.is_tensor(colors_left) else torch.as_tensor(np.asarray(colors_left))
+        if colors.dtype == torch.uint8:          # k / 255 from one table made on the host: the same fp32 values wherever the colours live
+            colors = torch.from_numpy((np.arange(256) / 255.0).astype(np.float32)).to(colors.device)[colors.long()]
+        return cls.from_raw(colors, depths, intrinsics, poses, bounds, color_masks=closed, **args)
+
     def _frame_tables(self, i: int):
         """(cdf [H*W] fp32, last kept pixel [] int64, colour-mask [H*W] bool) of frame ``i``; raises if its colour mask is empty
         (the reference's compaction would fail there as well, dataset.py:131-137)."""
@@ -455,6 +491,66 @@ def normalize_cameras(intrinsics, poses, scale_mat):
     out = c2w.clone()
     out[..., :3, 3] = ((c2w[..., :3, 3].double() - s[:3, 3]) / s[0, 0]).to(c2w.dtype)
     return k.clone(), out
+
+
+# ---- stereo pairs to depth frames (the reference's data/scared2019/preprocess.py:98-117, with the matcher it leaves to an external
+# network) -------------------------------------------------------------------------------------------------------------
+def disparity_to_depth(disp, disp_const, near=None, far=None) -> torch.Tensor:
+    """The depth of a disparity map as the reference's SCARED preprocessing derives it (preprocess.py:100-107): ``disp_const / disp``
+    where ``disp > 0`` and 0 elsewhere, then 0 where the depth is above ``far`` or below ``near`` (each may be None).  ``disp_const``
+    = focal length x baseline.  The quotient is taken in fp64 and rounded to fp32 once, the comparisons are made in fp64: the same
+    bits on the host and on the device.  Returns an fp32 tensor on ``disp``'s device."""
+    d = torch.as_tensor(disp, dtype=torch.float32)
+    seen = d > 0
+    depth = torch.where(seen, float(disp_const) / torch.where(seen, d, torch.ones_like(d)).double(), torch.zeros_like(d, dtype=torch.float64))
+    if far is not None:
+        depth = torch.where(depth.float().double() > float(far), torch.zeros_like(depth), depth)
+    if near is not None:
+        depth = torch.where(depth.float().double() < float(near), torch.zeros_like(depth), depth)
+    return depth.float()
+
+
+def close_mask(mask, k) -> torch.Tensor:
+    """Morphological closing of ``mask`` [..., H, W] with a ``k`` x ``k`` box, anchor at ``k // 2``: dilation (the maximum over the
+    reflected box) then erosion (the minimum over the box), the border never winning either extreme.  What the reference gets from
+    ``cv2.morphologyEx(depth_mask, cv2.MORPH_CLOSE, np.ones((k, k)))`` with ``k = int(w / 128)`` (preprocess.py:112-113); OpenCV is not
+    a dependency and the result is not pinned against it.  Two ``max_pool2d`` over a padding of -inf; the mask's dtype is kept."""
+    import torch.nn.functional as F
+    m = torch.as_tensor(mask)
+    k = int(k)
+    if k < 1 or m.dim() < 2:
+        raise ValueError(f"close_mask takes a mask [..., H, W] and k >= 1 (got {tuple(m.shape)}, k = {k})")
+    a, b = k // 2, k - 1 - k // 2
+    x = m.to(torch.float32).reshape(-1, 1, *m.shape[-2:])
+    inf = float("inf")
+    x = F.max_pool2d(F.pad(x, (b, a, b, a), value=-inf), k, 1)           # dilation: offsets -b .. a
+    x = -F.max_pool2d(F.pad(-x, (a, b, a, b), value=-inf), k, 1)         # erosion: offsets -a .. b
+    return x.reshape(m.shape).to(m.dtype)
+
+
+def stereo_depth(left, right, focal, baseline, max_disparity, near=None, far=None, close=None, engine=None, **matcher_args) -> Dict:
+    """A rectified stereo pair (or a stack of pairs) to depth: ``stereo.stereo_disparity`` -- census cost, semi-global matching,
+    uniqueness, left-right and speckle tests, sub-pixel disparity -- then ``disparity_to_depth`` with ``focal * baseline`` and the two
+    masks of the reference's preprocessing.  ``left`` / ``right`` [H,W(,3)] or [n,H,W(,3)], uint8 or float in [0,1]; the left image is
+    the reference view.  Device tensors go through ``Engine.stereo_disparity`` (csrc/stereo.hip; an ``Engine`` of their device is
+    made when none is given), anything else through the numpy twin; both give the same bits.  Returns tensors on the inputs' device:
+    ``disparity`` fp32 (0 = no match), ``depth`` fp32 (z-depth, ``depth_points``' convention; 0 = none), ``valid`` bool (the matcher's),
+    ``depth_mask`` bool (depth > 0) and ``color_mask`` bool (``close_mask(depth_mask, close or max(1, W // 128))``)."""
+    if _on_gpu(left, right):
+        engine = _engine_for(left, engine)
+        with torch.cuda.device(engine.device):
+            r = engine.stereo_disparity(left, right, max_disparity, **matcher_args)
+        disparity, valid = r["disparity"], r["valid"]
+    else:
+        from .stereo import stereo_disparity
+        as_np = lambda x: x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+        matcher_args.pop("poll", None)          # (how often the device's speckle filter reads its word back; the twin has none)
+        r = stereo_disparity(as_np(left), as_np(right), max_disparity, **matcher_args)
+        disparity, valid = torch.from_numpy(r["disparity"]), torch.from_numpy(r["valid"])
+    depth = disparity_to_depth(disparity, float(focal) * float(baseline), near, far)
+    depth_mask = depth > 0
+    k = int(close) if close else max(1, int(disparity.shape[-1]) // 128)
+    return {"disparity": disparity, "depth": depth, "valid": valid, "depth_mask": depth_mask, "color_mask": close_mask(depth_mask, k)}
 
 
 # ---- binary PLY files (the reference's demo writes its meshes through Open3D, trainer_endosurf.py:447-466; DESIGN.md 7e) ---------------

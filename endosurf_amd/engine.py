@@ -19,6 +19,7 @@ from .engine_geo import GeoMixin
 from .engine_kin import KinMixin
 from .engine_mesh import MeshMixin
 from .engine_reg import RegMixin
+from .engine_stereo import StereoMixin
 from .engine_trace import TraceMixin
 from .engine_track import TrackMixin
 
@@ -43,6 +44,7 @@ class PointCtx:
         return v
 
 
+@mixed_in(StereoMixin)
 @mixed_in(FuseMixin)
 @mixed_in(FlowMixin)
 @mixed_in(RegMixin)
