@@ -9,7 +9,7 @@
 //                     within a launch (one direction) every pixel lies on exactly one line, so each element has one owner; the first
 //                     direction stores instead of adding, so S needs no clearing.  The sum of integers is the same in any order.
 //   k_sgm_right       one wavefront per right-view pixel, lanes over d: dR = argmin_d S[y, x + d + dmin, d] over the columns that
-//                     exist, -1 for none; the argmin is the minimum of the keys (sum << 16 | d), so ties go to the smallest d
+//                     exist, -1 for none; the argmin is the minimum of the unsigned keys (sum << 16 | d), so ties go to the smallest d
 //   k_sgm_select      one wavefront per pixel, lanes over d (the row of D sums is one coalesced read): argmin by the same keys, the
 //                     second minimum for the uniqueness test, then lane 0: left-right check against dR, parabola sub-pixel (one
 //                     fp64 division, one fp64 addition), d0 / disparity / flags / valid
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void k_sgm_cost(const long long* __restrict__ 
     for (long long e = blockIdx.x * 256ll + threadIdx.x; e < total; e += gridDim.x * 256ll) {
         const long long p = e / D;
         const int d = (int)(e - p * D), x = (int)(p % W);
-        const int xr = x - dmin - d;
+        const int xr = x - dmin - d;          // (dmin <= 8192: no wrap)
         C[e] = xr < 0 ? (unsigned char)STEREO_OUTSIDE : (unsigned char)__popcll((unsigned long long)(cl[p] ^ cr[p - dmin - d]));
     }
 }
@@ -147,8 +147,16 @@ __global__ __launch_bounds__(256) void k_sgm_aggregate(const unsigned char* __re
     }
 }
 
-// The argmin of up to 256 sums spread over a wavefront, smallest d on ties: the minimum of the keys (sum << 16 | d); sums stay below 2^15.
-constexpr int STEREO_NO_KEY = 0x7fffffff;
+// The argmin of up to 256 sums spread over a wavefront, smallest d on ties: the minimum of the UNSIGNED keys (sum << 16 | d), which order
+// every uint16 sum; no key reaches STEREO_NO_KEY because d <= 255.  STEREO_NO_SUM is above every sum.
+constexpr unsigned STEREO_NO_KEY = 0xffffffffu;
+constexpr int STEREO_NO_SUM = 0x7fffffff;
+
+__device__ __forceinline__ unsigned wave_min(unsigned v) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v = min(v, __shfl_xor(v, o, 64));
+    return v;
+}
 
 __global__ __launch_bounds__(256) void k_sgm_right(const unsigned short* __restrict__ S, long long n_pix, int W, int D, int dmin,
                                                    int* __restrict__ dR) {
@@ -156,14 +164,14 @@ __global__ __launch_bounds__(256) void k_sgm_right(const unsigned short* __restr
     const long long n_waves = gridDim.x * 4ll;
     for (long long p = blockIdx.x * 4ll + (threadIdx.x >> 6); p < n_pix; p += n_waves) {          // one wavefront per right-view pixel
         const int x = (int)(p % W);
-        int key = STEREO_NO_KEY;
+        unsigned key = STEREO_NO_KEY;
 #pragma unroll
         for (int k = 0; k < STEREO_MAX_D / 64; ++k) {
-            const int d = lane + 64 * k;
-            if (d < D && x + dmin + d < W) key = min(key, ((int)S[(size_t)(p + dmin + d) * D + d] << 16) | d);
+            const int d = lane + 64 * k;          // (dmin <= 8192: x + dmin + d stays far inside int32)
+            if (d < D && x + dmin + d < W) key = min(key, ((unsigned)S[(size_t)(p + dmin + d) * D + d] << 16) | (unsigned)d);
         }
         key = wave_min(key);
-        if (lane == 0) dR[p] = key == STEREO_NO_KEY ? -1 : key & 0xffff;
+        if (lane == 0) dR[p] = key == STEREO_NO_KEY ? -1 : (int)(key & 0xffffu);
     }
 }
 
@@ -176,16 +184,16 @@ __global__ __launch_bounds__(256) void k_sgm_select(const unsigned short* __rest
     for (long long p = blockIdx.x * 4ll + (threadIdx.x >> 6); p < n_pix; p += n_waves) {          // one wavefront per pixel, lanes over d
         const unsigned short* s = S + (size_t)p * D;
         int v[STEREO_MAX_D / 64];
-        int key = STEREO_NO_KEY;
+        unsigned key = STEREO_NO_KEY;
 #pragma unroll
         for (int k = 0; k < STEREO_MAX_D / 64; ++k) {
             const int d = lane + 64 * k;
             v[k] = d < D ? (int)s[d] : -1;
-            if (d < D) key = min(key, (v[k] << 16) | d);
+            if (d < D) key = min(key, ((unsigned)v[k] << 16) | (unsigned)d);
         }
-        key = wave_min(key);
-        const int d0 = key & 0xffff, s0 = key >> 16;
-        int s2 = STEREO_NO_KEY;          // the smallest sum at least two disparities away from d0, STEREO_NO_KEY while there is none
+        key = wave_min(key);          // (D >= 1: some lane holds a key)
+        const int d0 = (int)(key & 0xffffu), s0 = (int)(key >> 16);
+        int s2 = STEREO_NO_SUM;          // the smallest sum at least two disparities away from d0, STEREO_NO_SUM while there is none
 #pragma unroll
         for (int k = 0; k < STEREO_MAX_D / 64; ++k) {
             const int d = lane + 64 * k;
@@ -194,7 +202,7 @@ __global__ __launch_bounds__(256) void k_sgm_select(const unsigned short* __rest
         s2 = wave_min(s2);
         if (lane != 0) continue;
         int f = 0;
-        if (s2 != STEREO_NO_KEY && s2 * (100 - uniqueness) < s0 * 100) f |= 1;          // (both products stay below 2^24)
+        if (s2 != STEREO_NO_SUM && s2 * (100 - uniqueness) < s0 * 100) f |= 1;          // (both products stay below 2^23)
         const int x = (int)(p % W), xr = x - dmin - d0;
         bool ok = xr >= 0;
         if (ok) {
@@ -233,7 +241,8 @@ __global__ __launch_bounds__(256) void k_speckle_sweep(const int* __restrict__ d
         for (int k = 0; k < 4; ++k) {
             if (!in[k]) continue;
             const int other = __atomic_load_n(label + nb[k], __ATOMIC_RELAXED);
-            if (other >= 0 && abs(d0[nb[k]] - d) <= range) best = min(best, other);
+            const long long diff = (long long)d0[nb[k]] - d;          // (64 bits: d0 is any int32)
+            if (other >= 0 && (diff < 0 ? -diff : diff) <= range) best = min(best, other);
         }
         // the pixel that ``best`` names is in this segment, so its label is too; a label is a pixel index of the same image, in range
         const int jump = __atomic_load_n(label + best, __ATOMIC_RELAXED);
@@ -321,7 +330,7 @@ int es_stereo_census(const unsigned char* grey, int n, int height, int width, lo
 int es_sgm_cost(const long long* census_left, const long long* census_right, int n, int height, int width, int max_disparity,
                 int min_disparity, unsigned char* cost, void* stream) {
     if (int e = stereo_shape("es_sgm_cost", n, height, width, max_disparity)) return e;
-    ES_REQUIRE(min_disparity >= 0, "es_sgm_cost: min_disparity must not be negative");
+    ES_REQUIRE(min_disparity >= 0 && min_disparity <= STEREO_MAX_SIZE, "es_sgm_cost: min_disparity must be in [0, 8192]");
     if (n == 0) return ST_OK;
     ES_REQUIRE(census_left && census_right && cost, "es_sgm_cost: null buffer (census_left, census_right, cost)");
     ES_REQUIRE(aligned(census_left, 8) && aligned(census_right, 8), "es_sgm_cost: census_left and census_right must be 8-byte aligned");
@@ -360,7 +369,7 @@ int es_sgm_select(const unsigned short* sums, int n, int height, int width, int 
                   int lr_max, int subpixel, int* d0, float* disparity, unsigned char* flags, unsigned char* valid, void* scratch,
                   void* stream) {
     if (int e = stereo_shape("es_sgm_select", n, height, width, max_disparity)) return e;
-    ES_REQUIRE(min_disparity >= 0, "es_sgm_select: min_disparity must not be negative");
+    ES_REQUIRE(min_disparity >= 0 && min_disparity <= STEREO_MAX_SIZE, "es_sgm_select: min_disparity must be in [0, 8192]");
     ES_REQUIRE(uniqueness >= 0 && uniqueness <= 100, "es_sgm_select: uniqueness must be in [0, 100]");
     ES_REQUIRE(lr_max >= 0, "es_sgm_select: lr_max must not be negative");
     if (n == 0) return ST_OK;

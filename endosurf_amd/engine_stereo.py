@@ -94,7 +94,7 @@ class StereoMixin:
         return {k: v[0] for k, v in out.items()} if single else out
 
     def sgm_select(self, S, min_disparity=0, uniqueness=10, lr_max=1, subpixel=True):
-        """``stereo.select`` without the speckle filter: S uint16 [n,H,W,D] (or [H,W,D]) on this device -> dict(disparity fp32, valid
+        """``stereo.select`` without the speckle filter: S uint16 [n,H,W,D] (or [H,W,D]) on this device, any values -> dict(disparity fp32, valid
         bool, d0 int32, flags uint8), each [n,H,W] ([H,W])."""
         if not torch.is_tensor(S) or S.dtype != torch.uint16 or S.dim() not in (3, 4) or S.device != self.device:
             raise ValueError(f"Engine.sgm_select takes S uint16 [n, H, W, D] or [H, W, D] on {self.device}")
@@ -131,7 +131,7 @@ class StereoMixin:
                                         ptr(out.get("flags")), st), "es_speckle_apply")
 
     def speckle_filter(self, d0, valid, size, range=1, poll=8):
-        """``stereo.speckle_keep``: d0 integer and valid bool, [n,H,W] or [H,W] -> bool of the same shape, the valid pixels whose
+        """``stereo.speckle_keep``: d0 integer (any int32) and valid bool, [n,H,W] or [H,W] -> bool of the same shape, the valid pixels whose
         segment (valid 4-neighbours with |d0 - d0'| <= ``range``) has at least ``size`` pixels.  Labels are propagated by sweeps, one
         launch each; the host reads one word every ``poll`` sweeps.  The same bits for any ``poll``."""
         size, max_diff = stereo.check_matcher(1, speckle_size=size, speckle_range=range)[7:9]

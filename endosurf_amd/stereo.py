@@ -29,8 +29,8 @@ def check_matcher(max_disparity, min_disparity=0, p1=7, p2=60, paths=8, uniquene
     uniqueness, lr_max, speckle_size, speckle_range = int(uniqueness), int(lr_max), int(speckle_size), int(speckle_range)
     if not 1 <= D <= MAX_DISPARITIES:
         raise ValueError(f"max_disparity must be in [1, {MAX_DISPARITIES}] (got {D})")
-    if dmin < 0:
-        raise ValueError(f"min_disparity must not be negative (got {dmin})")
+    if not 0 <= dmin <= MAX_SIZE:          # (every min_disparity >= W already means "no column", so the bound loses nothing)
+        raise ValueError(f"min_disparity must be in [0, {MAX_SIZE}] (got {dmin})")
     if not 0 <= p1 <= p2 <= MAX_PENALTY:
         raise ValueError(f"the penalties must satisfy 0 <= p1 <= p2 <= {MAX_PENALTY} (got p1 {p1}, p2 {p2})")
     if paths not in (4, 8):
@@ -126,7 +126,8 @@ def path_costs(C, direction, p1=7, p2=60) -> np.ndarray:
 
 
 def aggregate(C, p1=7, p2=60, paths=8) -> np.ndarray:
-    """S [H,W,D] uint16 = the sum of the path costs of ``DIRECTIONS[:paths]``; at most paths (63 + P2)."""
+    """S [H,W,D] uint16 = the sum of the path costs of ``DIRECTIONS[:paths]``; at most paths (max C + P2): 8 (63 + P2) for a census
+    cost, 8 (255 + 1024) = 10232 for any byte volume."""
     S = np.zeros(np.shape(C), np.int32)
     for r in DIRECTIONS[:int(paths)]:
         S += path_costs(C, r, p1, p2)

@@ -1,13 +1,17 @@
 """GPU: the stereo matcher on the device (csrc/stereo.hip) against its numpy twin, bit for bit on every element: census,
 S, d0, flags, valid and the disparity's fp32 bits on every case of ``stereo_util`` and both image kinds; the speckle filter for any
-polling interval; batching and chunking; repeatability; and ``stereo_depth`` / ``FrameSet.from_stereo`` on the analytic scenes."""
+polling interval; batching and chunking; repeatability; and ``stereo_depth`` / ``FrameSet.from_stereo`` on the analytic scenes.  The
+sweep (``stereo_util.SWEEP``) runs every stage over the argument space the matcher admits, and the stage tests give each entry of the
+C ABI inputs that only its contract bounds -- any int64 census word, any cost byte, any uint16 sum, any int32 d0 -- still bit for bit."""
 import numpy as np
 import pytest
 import torch
 
 import stereo_util as U
+from endosurf_amd import _lib
 from endosurf_amd import data as DT
 from endosurf_amd import stereo as ST
+from endosurf_amd._lib import check, ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -76,6 +80,123 @@ def test_speckle_filter_for_any_poll(eng, q):
             got = eng.speckle_filter(d0, valid, U.SPECKLE_SIZE, r, poll=poll)
             assert got.dtype == torch.bool and np.array_equal(host(got), c["speckle"][r]), (r, poll)
     assert torch.equal(d0, dev(sel["d0"])) and torch.equal(valid, dev(sel["valid"]))          # the inputs are left alone
+
+
+# ---- the stages through the C ABI, where Engine has no method for one -------------------------------------------------------------------------
+def abi_cost(census_left, census_right, D, dmin):
+    """es_sgm_cost called directly: two int64 [H,W] arrays -> C uint8 [H,W,D] numpy."""
+    lib, st = _lib.load(), _lib.stream_ptr()
+    H, W = census_left.shape
+    cl, cr = dev(census_left), dev(census_right)
+    cost = torch.full((H, W, D), 0xAA, device="cuda", dtype=torch.uint8)
+    check(lib.es_sgm_cost(ptr(cl), ptr(cr), 1, H, W, D, dmin, ptr(cost), st), "es_sgm_cost")
+    return host(cost)
+
+
+def abi_aggregate(C, p1, p2, paths):
+    """es_sgm_aggregate called directly on a given cost volume: uint8 [H,W,D] -> S uint16 [H,W,D] numpy."""
+    lib, st = _lib.load(), _lib.stream_ptr()
+    H, W, D = C.shape
+    cost = dev(C)
+    sums = torch.full((H, W, D), 0x5555, device="cuda", dtype=torch.int16)          # (never cleared: the first direction stores)
+    check(lib.es_sgm_aggregate(ptr(cost), 1, H, W, D, p1, p2, paths, ptr(sums), st), "es_sgm_aggregate")
+    return host(sums).view(np.uint16)
+
+
+def same_array(got, want, what):
+    assert got.dtype == want.dtype and got.shape == want.shape, what
+    assert np.array_equal(got, want), (what, int((got != want).sum()))
+
+
+# ---- the argument sweep --------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("i", range(len(U.SWEEP)), ids=[U.sweep_id(q) for q in U.SWEEP])
+def test_sweep_against_the_twin(eng, i):
+    H, W, D, dmin, p1, p2, paths, uniqueness, lr_max, size, srange, kind = U.SWEEP[i]
+    c = U.sweep_case(i)
+    for side in ("left", "right"):
+        same_array(host(eng.census(dev(c[side]))), c["census_" + side], "census " + side)
+    same_array(abi_cost(c["census_left"], c["census_right"], D, dmin), c["C"], "cost")
+    same_array(abi_aggregate(c["C"], p1, p2, paths), c["S"], "aggregate")
+    S = eng.sgm_volume(dev(c["left"]), dev(c["right"]), D, dmin, p1, p2, paths)
+    assert S.dtype == torch.uint16
+    same_array(host(S), c["S"], "S")
+    same_select(eng.sgm_select(S, dmin, uniqueness, lr_max, True), c["select"])
+    same_select(eng.sgm_select(S, dmin, uniqueness, lr_max, False), c["select_whole"])
+    for poll in (1, 1000):
+        full = eng.stereo_disparity(dev(c["left"]), dev(c["right"]), D, dmin, p1, p2, paths, uniqueness, lr_max, True, size, srange, poll=poll)
+        same_select(full, c["full"])
+
+
+# ---- each stage on inputs only its contract bounds -----------------------------------------------------------------------------------------------
+WORDS = {"uniform": lambda rng, shape: rng.integers(-2 ** 63, 2 ** 63, shape, dtype=np.int64), "ones": lambda rng, shape: np.full(shape, -1, np.int64),
+         "sign": lambda rng, shape: np.full(shape, -2 ** 63, np.int64), "zero": lambda rng, shape: np.zeros(shape, np.int64)}
+WORD_PAIRS = [("uniform", "uniform"), ("ones", "uniform"), ("uniform", "sign"), ("ones", "sign"), ("sign", "ones"), ("ones", "zero")]
+
+
+@pytest.mark.parametrize("shape", [(5, 9), (12, 70)], ids=["5x9", "12x70"])
+@pytest.mark.parametrize("D", [7, 65])
+@pytest.mark.parametrize("dmin", [0, 2])
+def test_cost_of_any_census_words(shape, D, dmin):
+    rng = np.random.default_rng([2026, 500 + 100 * dmin + D + shape[0]])
+    top = 0
+    for left, right in WORD_PAIRS:
+        cl, cr = WORDS[left](rng, shape), WORDS[right](rng, shape)
+        want = ST.cost_volume(cl, cr, D, dmin)
+        same_array(abi_cost(cl, cr, D, dmin), want, (left, right))
+        top = max(top, int(want.max()))
+    assert top == 64          # (all ones against zero: beyond the 62 bits a census sets)
+
+
+@pytest.mark.parametrize("shape", [(9, 11, 4), (6, 13, 65), (5, 9, 256)], ids=lambda s: "x".join(map(str, s)))
+def test_aggregate_of_any_bytes(shape):
+    C = np.random.default_rng([2026, 600 + shape[2]]).integers(0, 256, shape, dtype=np.uint8)
+    for p1, p2 in ((0, 0), (0, 1024), (1024, 1024), (7, 60)):
+        for paths in (4, 8):
+            want = ST.aggregate(C, p1, p2, paths)
+            same_array(abi_aggregate(C, p1, p2, paths), want, (p1, p2, paths))
+            assert int(want.max()) > 63 * paths
+
+
+def test_aggregate_reaches_the_largest_sum():
+    C = U.saturating_volume()
+    for paths, top in ((8, 10232), (4, 5116)):
+        got = abi_aggregate(C, 1024, 1024, paths)
+        same_array(got, ST.aggregate(C, 1024, 1024, paths), paths)
+        assert int(got.max()) == top and (got[6, 6, 1:] == top).all()
+
+
+@pytest.mark.parametrize("D", U.SELECT_D)
+@pytest.mark.parametrize("kind", U.SELECT_VOLUMES)
+def test_select_of_any_uint16_sums(eng, kind, D):
+    want_S = U.select_volume(kind, D)
+    S = dev(want_S.view(np.int16)).view(torch.uint16)
+    for dmin in (0, 3, U.SELECT_W):
+        for uniqueness in (0, 10, 100):
+            for lr_max in (0, 1000):
+                for subpixel in (True, False):
+                    same_select(eng.sgm_select(S, dmin, uniqueness, lr_max, subpixel), ST.select(want_S, dmin, uniqueness, lr_max, subpixel))
+    assert torch.equal(S.view(torch.int16), dev(want_S.view(np.int16)))          # the sums are left alone
+
+
+FIELDS = U.speckle_fields()
+
+
+@pytest.mark.parametrize("field", FIELDS, ids=[f[0] for f in FIELDS])
+def test_speckle_filter_on_hand_made_fields(eng, field):
+    name, d0, valid, size, srange, want = field
+    assert np.array_equal(ST.speckle_keep(d0, valid, size, srange), want)
+    for poll in (1, 7, 1000):
+        got = eng.speckle_filter(dev(d0), dev(valid), size, srange, poll=poll)
+        assert got.dtype == torch.bool and tuple(got.shape) == valid.shape and np.array_equal(host(got), want), (name, poll)
+
+
+def test_speckle_segments_stay_inside_their_image_and_row(eng):
+    d0, valid, want = U.speckle_stack()
+    for size, keep in want.items():
+        for poll in (1, 7, 1000):
+            got = eng.speckle_filter(dev(d0), dev(valid), size, 0, poll=poll)
+            assert np.array_equal(host(got), keep), (size, poll)
+            assert np.array_equal(host(got), np.stack([ST.speckle_keep(d0[i], valid[i], size, 0) for i in range(2)]))
 
 
 def test_a_stack_equals_its_pairs(eng):

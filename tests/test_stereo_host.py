@@ -1,5 +1,6 @@
 """CPU: the stereo matcher's numpy twin (endosurf_amd/stereo.py) on analytic scenes with ground truth in closed form and
-on the algebra its rules imply; ``disparity_to_depth`` against the reference's rule restated here; ``close_mask``'s properties; and the
+on the algebra its rules imply; the path recurrence against a scalar restatement of the header's formula; what the device tests' argument
+sweep, uint16 volumes and speckle fields cover, as conditions on those inputs; ``disparity_to_depth`` against the reference's rule restated here; ``close_mask``'s properties; and the
 refusals of the library's stereo entries, which come before any launch."""
 import ctypes as C
 
@@ -135,6 +136,35 @@ def test_speckle_against_a_flood_fill(p):
     assert np.array_equal(ST.speckle_keep(d0, valid, 13, 0), valid) and not ST.speckle_keep(d0, valid, 14, 0).any()
 
 
+FIELDS = U.speckle_fields()
+
+
+@pytest.mark.parametrize("field", FIELDS, ids=[f[0] for f in FIELDS])
+def test_speckle_on_hand_made_fields(field):
+    name, d0, valid, size, srange, want = field
+    got = ST.speckle_keep(d0, valid, size, srange)
+    assert np.array_equal(got, flood_keep(d0, valid, size, srange)) and np.array_equal(got, want), name
+
+
+def test_speckle_fields_are_what_they_claim():
+    by_name = {f[0]: f for f in FIELDS}
+    snake = by_name["snake-159"][2]
+    assert snake.shape == (9, 31) and int(snake.sum()) == 159 and snake[0::2].all() and np.array_equal(by_name["snake-159"][5], snake)
+    assert not by_name["snake-160"][5].any()
+    d0 = by_name["extreme-row"][1]
+    assert d0.dtype == np.int32 and d0.tolist() == [[2 ** 31 - 1, -2 ** 31, 5, 6]] and by_name["extreme-row"][5].tolist() == [[False, False, True, True]]
+    with np.errstate(over="ignore"):          # in 32 bits the first difference wraps to 1: a sweep that subtracts in int32 keeps all four
+        assert np.abs(d0[0, :1] - d0[0, 1:2]).tolist() == [1]
+    assert np.array_equal(by_name["size-0"][5], by_name["size-0"][2])
+    d0, valid, want = U.speckle_stack()
+    for size, keep in want.items():
+        per_image = np.stack([ST.speckle_keep(d0[i], valid[i], size, 0) for i in range(2)])
+        assert np.array_equal(per_image, keep) and np.array_equal(per_image, np.stack([flood_keep(d0[i], valid[i], size, 0) for i in range(2)])), size
+    # ... and a filter that ran over the stack as one 8 x 5 image, or over each image as one row of 20, would answer differently
+    assert not np.array_equal(ST.speckle_keep(d0.reshape(8, 5), valid.reshape(8, 5), 6, 0).reshape(2, 4, 5), want[6])
+    assert not np.array_equal(np.stack([ST.speckle_keep(d0[i].reshape(1, 20), valid[i].reshape(1, 20), 2, 0).reshape(4, 5) for i in range(2)]), want[2])
+
+
 def test_stereo_errors():
     d = np.array([[1.0, 2.0, 0.0, 4.0]], np.float32)
     e = ST.stereo_errors(d, d > 0, np.array([[1.25, 4.0, 3.0, 4.0]]), np.array([[True, True, True, False]]), thresholds=(0.5, 1))
@@ -148,6 +178,105 @@ def test_matcher_arguments_are_checked():
                 dict(max_disparity=8, lr_max=-1), dict(max_disparity=8, speckle_size=-1)):
         with pytest.raises(ValueError):
             ST.check_matcher(**bad)
+
+
+def test_min_disparity_is_bounded_by_the_largest_image_side():
+    for dmin in (8193, 2 ** 31 - 1):
+        with pytest.raises(ValueError, match="min_disparity"):
+            ST.check_matcher(8, min_disparity=dmin)
+    assert ST.check_matcher(8, min_disparity=8192)[1] == 8192
+    # nothing is lost: from W on, every min_disparity means "no column", so every cost is 63 and every pixel fails left-right
+    l, r = U.pair(6, 9, 4, 0, "noise")
+    at_w, beyond = (ST.stereo_disparity(l, r, 4, dmin) for dmin in (9, 8192))
+    assert (ST.sgm_volume(l, r, 4, 9) == ST.sgm_volume(l, r, 4, 8192)).all() and (ST.cost_volume(ST.census(l), ST.census(r), 4, 9) == 63).all()
+    for k in ("valid", "d0", "flags"):
+        assert np.array_equal(at_w[k], beyond[k]), k
+    assert not beyond["valid"].any() and (beyond["flags"] & ST.FLAG_LEFT_RIGHT).all()
+
+
+# ---- 2b. the recurrence restated, the largest sums, and what the sweep and the stage volumes cover ---------------------------------------------
+SCALAR_SHAPES = [(6, 7, 5), (4, 5, 1), (3, 6, 2), (1, 7, 4), (6, 1, 3), (1, 1, 1), (5, 4, 3)]
+SCALAR_PENALTIES = [(0, 0), (0, 5), (7, 60), (1024, 1024)]
+
+
+@pytest.mark.parametrize("shape", SCALAR_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_path_costs_against_a_scalar_restatement(shape):
+    C = np.random.default_rng([2026, 400 + SCALAR_SHAPES.index(shape)]).integers(0, 256, shape, dtype=np.uint8)
+    for p1, p2 in SCALAR_PENALTIES:
+        total = np.zeros(shape, np.int64)
+        for r in ST.DIRECTIONS:
+            want = np.array(U.path_costs_scalar(C.tolist(), r, p1, p2), np.int64).reshape(shape)
+            got = ST.path_costs(C, r, p1, p2)
+            assert np.array_equal(got, want), (r, p1, p2, int((got != want).sum()))
+            total += want
+            if r == ST.DIRECTIONS[3]:
+                assert np.array_equal(ST.aggregate(C, p1, p2, 4), total)
+        assert np.array_equal(ST.aggregate(C, p1, p2, 8), total)
+
+
+def test_saturating_volume_reaches_the_largest_sum():
+    C = U.saturating_volume()
+    S8, S4 = ST.aggregate(C, 1024, 1024, 8), ST.aggregate(C, 1024, 1024, 4)
+    assert S8.dtype == np.uint16 and int(S8.max()) == 8 * (255 + 1024) == 10232 and int(S4.max()) == 4 * (255 + 1024) == 5116
+    assert (S8[6, 6, 1:] == 10232).all() and S8[6, 6, 0] == 0
+    for r in ST.DIRECTIONS:
+        assert np.array_equal(ST.path_costs(C, r, 1024, 1024), np.array(U.path_costs_scalar(C.tolist(), r, 1024, 1024)))
+
+
+def test_sweep_covers_what_it_claims():
+    """Conditions on the sweep's inputs, by the twin alone: what tests/test_gpu_stereo.py can only catch if it occurs."""
+    assert len(U.SWEEP) >= U.SWEEP_DRAWN and U.SWEEP[:U.SWEEP_DRAWN] == [U._draw(i) for i in range(U.SWEEP_DRAWN)]
+    on = off = 0
+    kd_paths, seen = set(), {k: 0 for k in ("no_right_column", "tie", "subpixel", "p2_1024", "dmin_past_w", "speckle", "p_zero", "p1_is_p2")}
+    for i, q in enumerate(U.SWEEP):
+        H, W, D, dmin, p1, p2, paths, uniqueness, lr_max, size, srange, kind = q
+        assert 1 <= H <= 24 and 1 <= W <= 140 and H * W * D <= U.SWEEP_MAX_CELLS and D in U.SWEEP_D and kind in U.SWEEP_KINDS
+        ST.check_matcher(D, dmin, p1, p2, paths, uniqueness, lr_max, size, srange)
+        c = U.sweep_case(i)
+        f = c["full"]["flags"].reshape(-1)
+        on |= int(np.bitwise_or.reduce(f))
+        off |= int(np.bitwise_or.reduce(~f & 7))
+        kd_paths.add(((D + 63) // 64, paths))
+        Si = c["S"].astype(np.int64)
+        d0 = Si.argmin(-1)
+        seen["no_right_column"] += bool((c["dR"] == -1).any())
+        seen["tie"] += bool(((Si == Si.min(-1, keepdims=True)).sum(-1) > 1).any())
+        seen["subpixel"] += bool(((d0 > 0) & (d0 < D - 1)).any())
+        seen["p2_1024"] += p2 == 1024
+        seen["dmin_past_w"] += dmin >= W
+        seen["speckle"] += bool((f & ST.FLAG_SPECKLE).any())
+        seen["p_zero"] += p1 == 0 == p2
+        seen["p1_is_p2"] += p1 == p2
+    print(f"\n{len(U.SWEEP)} configurations: flags set {on}, clear {off}; {seen}")
+    assert on == 7 and off == 7, (on, off)
+    assert kd_paths == {(kd, paths) for kd in (1, 2, 3, 4) for paths in (4, 8)}, sorted(kd_paths)
+    assert all(seen.values()), seen
+    for name, values in (("uniqueness", (0, 100)), ("lr_max", (0,)), ("size", (0, 1))):
+        col = {"uniqueness": 7, "lr_max": 8, "size": 9}[name]
+        assert set(values) <= {q[col] for q in U.SWEEP}, name
+    assert any(q[8] >= q[2] for q in U.SWEEP) and any(q[9] > q[0] * q[1] for q in U.SWEEP) and any(q[10] == 300 for q in U.SWEEP)
+
+
+def signed_key_argmin(S):
+    """What a 32-bit SIGNED key ``S << 16 | d`` picks: the argmin the device took before its keys became unsigned."""
+    keys = ((S.astype(np.int64) << 16) | np.arange(S.shape[-1])).astype(np.uint32).view(np.int32)
+    return keys.min(-1) & 0xffff, keys.min(-1) >> 16
+
+
+def test_select_volumes_tell_signed_keys_from_unsigned():
+    """The volumes of the device test order differently under signed 32-bit keys, so that test fails on a library with such keys."""
+    for D in U.SELECT_D:
+        for kind in U.SELECT_VOLUMES:
+            S = U.select_volume(kind, D)
+            assert S.dtype == np.uint16 and S.shape == (U.SELECT_H, U.SELECT_W, D)
+            d0, s0 = signed_key_argmin(S)
+            want = S.astype(np.int64).argmin(-1)
+            if kind in ("uniform", "edge") and D >= 2:
+                assert (d0 != want).mean() > 0.25, (kind, D)          # (about half the pixels at D = 2, nearly all at large D)
+            if kind in ("max", "high"):          # the argmin survives, the minimum read back by an arithmetic shift does not
+                assert np.array_equal(d0, want) and (s0 < 0).all() and int(S.min()) >= 32768
+    half = U.select_volume("uniform", 65) >> 1
+    assert np.array_equal(signed_key_argmin(half)[0], half.astype(np.int64).argmin(-1))
 
 
 # ---- 3. disparity to depth ----------------------------------------------------------------------------------------------------------------------
@@ -257,6 +386,7 @@ REFUSALS = [
     (dict(D=0), WITH_D, b"max_disparity"), (dict(D=257), WITH_D, b"max_disparity"),
     (dict(n=2, H=4096, W=4096, D=64), WITH_D, b"n H W D"), (dict(n=1, H=4096, W=2048, D=256), WITH_D, b"n H W D"),
     (dict(dmin=-1), ("es_sgm_cost", "es_sgm_select"), b"min_disparity"),
+    (dict(dmin=8193), ("es_sgm_cost", "es_sgm_select"), b"min_disparity"), (dict(dmin=2**31 - 1), ("es_sgm_cost", "es_sgm_select"), b"min_disparity"),
     (dict(p1=-1), ("es_sgm_aggregate",), b"p1"), (dict(p1=61), ("es_sgm_aggregate",), b"p1"), (dict(p2=1025), ("es_sgm_aggregate",), b"p2"),
     (dict(paths=5), ("es_sgm_aggregate",), b"paths"), (dict(paths=0), ("es_sgm_aggregate",), b"paths"),
     (dict(uniqueness=-1), ("es_sgm_select",), b"uniqueness"), (dict(uniqueness=101), ("es_sgm_select",), b"uniqueness"),
